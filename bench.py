@@ -1,9 +1,15 @@
 #!/usr/bin/env python3
 """bench.py — CelebA-128 cold-diffusion training throughput (+ 200-step sampling latency) on MI355X.
 
-  python bench.py --gpus 1 --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, runs W warm-up and K timed optimizer steps and prints the headline line (`value` img/s, `ms_per_step`).
+--dump-outputs DIR writes what the last timed step produced (its loss, and a fixed seeded sample of the parameters, Adam moments
+and EMA weights it left behind) as DIR/<name>.npy.  --full adds everything else the benchmark measures: the GEMM roofline pass,
+step / per-class roofline figures, the gradient-exchange record (N > 1), the 200-step sampler, the unfused step, the self-check
+against the CPU oracle, the bf16 / f32 mode lines, BASELINE configs 1, 2, 4 and 5 and the CPU baseline.
 
 Workload (BASELINE.json config 3, the single-GPU CelebA-128 case):
   Unet(dim=64, dim_mults=(1,2,4,8), channels=3) at 128x128, denoising GaussianDiffusion(T=200,
@@ -21,6 +27,7 @@ import argparse
 import json
 import os
 import sys
+import tempfile
 import time
 
 REPO = os.path.dirname(os.path.abspath(__file__))
@@ -41,6 +48,8 @@ def log(msg):
 
 
 _T0 = time.perf_counter()
+# Trainer(results_folder=) creates the folder; the benchmark never saves or samples into it, so it is a throw-away directory
+_RESULTS = tempfile.TemporaryDirectory(prefix="colddiff_bench_")
 PEAK_F32_MFMA_TFLOPS = 157.3       # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32, dense
 PEAK_BF16_MFMA_TFLOPS = 2500.0     # MI355X_MICROARCH.md: v_mfma_f32_32x32x16_bf16, dense
 PEAK_HBM_GBS = 8000.0              # MI355X_MICROARCH.md: HBM3E
@@ -97,7 +106,7 @@ def build_workload(args, device):
                                   sampling_routine='x0_step_down').to(device)
     trainer = Trainer(diffusion, None, image_size=128, train_batch_size=args.batch, train_lr=2e-5, train_num_steps=10 ** 9,
                       gradient_accumulate_every=args.accum, ema_decay=0.995, fp16=False, dataset='synthetic',
-                      results_folder=os.path.join(REPO, "gpurun_out", "bench_results"))
+                      results_folder=_RESULTS.name)
     trainer.quiet = True
     return model, diffusion, trainer
 
@@ -221,7 +230,7 @@ def cpu_baseline(args):
     import contextlib
     import io
     ncores = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
-    ncores = max(1, min(ncores, 64))
+    ncores = max(1, min(ncores, 64, int(os.environ.get("OMP_NUM_THREADS") or 64)))     # a CPU allowance set for the process wins
     torch.set_num_threads(ncores)
     torch.manual_seed(123457)
     with contextlib.redirect_stdout(io.StringIO()):
@@ -356,7 +365,7 @@ def secondary_workloads(device):
     from colddiff.trainer import Trainer
     out = {}
     quiet = lambda: contextlib.redirect_stdout(io.StringIO())
-    res = os.path.join(REPO, "gpurun_out", "bench_results")
+    res = _RESULTS.name
     # ---- config 4: CelebA-128 deblurring, Exponential_reflect T=200 k=15 std=0.01 (celebA_128.py) ------------------------
     from deblurring_diffusion_pytorch import GaussianDiffusion, Model, Unet
     torch.manual_seed(123457)
@@ -554,6 +563,30 @@ def tail_ms_per_step(profile_name="kernel_trace.json"):
             "include initialisation copies / packs)", "provenance": prov}
 
 
+DUMP_SAMPLE = 1 << 21          # arena elements sampled per dumped state vector (4 x 8 MB of float32)
+DUMP_SEED = 20240913
+
+
+def dump_outputs(folder, trainer, loss):
+    """What the last timed optimizer step hands its caller: the step's loss, and the state it leaves behind -- parameters, Adam's
+    two moments, the EMA weights.  The flat arenas hold 56.6 M values each, so the same fixed, seeded set of DUMP_SAMPLE positions
+    (sorted) is taken from every one of them; `sample_index.npy` records those positions."""
+    import numpy as np
+    os.makedirs(folder, exist_ok=True)
+    n = trainer.arena.numel
+    idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, n, size=min(DUMP_SAMPLE, n)))
+    sel = torch.from_numpy(idx).to(trainer.arena.data.device)
+    arrays = {"loss": loss.detach().float().reshape(1),
+              "params_sample": trainer.arena.data[sel],
+              "adam_exp_avg_sample": trainer.opt.exp_avg[sel],
+              "adam_exp_avg_sq_sample": trainer.opt.exp_avg_sq[sel],
+              "ema_params_sample": trainer.ema_arena.data[sel]}
+    for name, t in arrays.items():
+        np.save(os.path.join(folder, name + ".npy"), t.cpu().numpy().astype(np.float32))
+    np.save(os.path.join(folder, "sample_index.npy"), idx.astype(np.float64))
+    log(f"outputs of the last timed step written to {folder}: {', '.join(sorted(arrays))}, sample_index")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -565,6 +598,11 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-sample", action="store_true")
     ap.add_argument("--no-secondary", action="store_true", help="skip the bf16-mode line, the config 1 / 2 / 4 / 5 secondary workloads and the self-check")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's loss and a seeded sample of the state it leaves as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline figure: roofline pass, sampler, unfused step, self-check, "
+                         "bf16 / f32 lines, secondary workloads, CPU baseline (each --no-* option still drops its part)")
     args = ap.parse_args()
 
     from colddiff import parallel, runtime
@@ -580,8 +618,8 @@ def main():
 
     log(f"building workload on {device} (world {world})")
     model, diffusion, trainer = build_workload(args, device)
-    timer = GemmTimer(runtime.lib())
-    use_timer = os.environ.get("CDF_BENCH_NOTIMER", "0") != "1"
+    timer = GemmTimer(runtime.lib()) if args.full else None
+    use_timer = args.full and os.environ.get("CDF_BENCH_NOTIMER", "0") != "1"
     log("workload built")
 
     def barrier():
@@ -596,8 +634,9 @@ def main():
         log(f"warm-up step {i} done")
     barrier()
     t0 = time.perf_counter()
+    loss = None
     for _ in range(args.steps):
-        trainer.train_step()
+        loss = trainer.train_step()
         trainer.step += 1
     barrier()
     elapsed = time.perf_counter() - t0
@@ -606,12 +645,14 @@ def main():
         tt = torch.tensor([elapsed], device=device, dtype=torch.float64)
         torch.distributed.all_reduce(tt, op=torch.distributed.ReduceOp.MAX)
         elapsed = tt.item()
+    if args.dump_outputs and parallel.rank() == 0 and loss is not None:
+        dump_outputs(args.dump_outputs, trainer, loss)        # before any --full pass below runs further steps on the same weights
 
     # Roofline pass: the SAME K steps again, now with a HIP-event pair around every MFMA GEMM launch (on the launch
     # stream).  Kept out of the timed region above because ~1000 event records per step cost 3 % of throughput; the
     # instrumented steps' own wall time is reported next to the kernel figures.
     dp_stats = None
-    if world > 1 and trainer.sync is not None:
+    if args.full and world > 1 and trainer.sync is not None:
         # how much of the gradient exchange the backward pass hides: a few further steps with events around every bucket's all-reduce
         trainer.sync.profile = True
         barrier()
@@ -636,8 +677,8 @@ def main():
 
     imgs_per_step = args.batch * args.accum * world
     value = imgs_per_step * args.steps / elapsed
-    kernels = timer.summary(args.steps, elapsed_instr if elapsed_instr else elapsed)
-    if os.environ.get("CDF_BENCH_SHAPES"):
+    kernels = timer.summary(args.steps, elapsed_instr if elapsed_instr else elapsed) if timer else {}
+    if timer and os.environ.get("CDF_BENCH_SHAPES"):
         timer.dump_shapes(args.steps)
 
     out = {
@@ -656,7 +697,7 @@ def main():
         out["gradient_exchange"] = dict(dp_stats, backend=torch.distributed.get_backend(),
                                         note="sum all-reduce of the flat fp32 gradient arena, bucketed in runs of whole tensors, issued on a side "
                                              "stream during backward of the last accumulation micro-step; exposed = after backward ended")
-    if parallel.rank() == 0:
+    if parallel.rank() == 0 and args.full:
         dom = max(kernels, key=lambda k: kernels[k]["share_of_step"]) if kernels else None
         if dom:
             d = kernels[dom]
@@ -797,6 +838,7 @@ def main():
             log("secondary workloads done")
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args)
+    if parallel.rank() == 0:
         print(json.dumps(out), flush=True)
     if world > 1:
         torch.distributed.barrier()

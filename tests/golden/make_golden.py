@@ -480,8 +480,157 @@ def evaluation_cases(net_sd):
     return out
 
 
+def sampler_cases():
+    """The reference side of tests/test_oracle.py::test_oracle_vs_live_reference_degradations_and_samplers, same seeds and calls:
+    q_sample + sample of the four packages at 24 x 24 with a Unet(dim=8, (1, 2)) -> live_samplers.pt.  Kept small: the seeded
+    weights are stored as their sd_digest (the test redraws them), every output the test compares bit for bit as its tensor_digest,
+    and only the network outputs it compares to a tolerance as values, each distinct tensor once."""
+    import contextlib
+    import io
+    S, B = 24, 2
+    g = torch.Generator().manual_seed(4242)
+    x = torch.randint(0, 256, (B, 3, S, S), generator=g).float() / 255 * 2 - 1
+    quiet = lambda: contextlib.redirect_stdout(io.StringIO())
+    shared = {}
+    keep = lambda t: shared.setdefault(tensor_digest(t), t.clone())      # (the same object -> torch.save stores it once)
+    walk = lambda r: [tensor_digest(r[0]), keep(r[1]), keep(r[2])]       # (x_t or the start: exact; direct, img: values)
+    ref = ref_shim.load("deblurring")
+    torch.manual_seed(99)
+    with quiet():
+        rnet = ref.Unet(dim=8, dim_mults=(1, 2), channels=3)
+    out = {"x": x, "sd_sha256": sd_digest(rnet.state_dict())}
+    with torch.no_grad(), quiet():
+        for routine, ks, std in (("Incremental", 5, 0.3), ("Exponential_reflect", 7, 0.05)):
+            for sampling in ("default", "x0_step_down"):
+                T, t = 6, torch.tensor([5, 2])
+                d = ref.GaussianDiffusion(rnet, image_size=S, device_of_kernel="cpu", channels=3, timesteps=T, kernel_std=std, kernel_size=ks,
+                                          blur_routine=routine, sampling_routine=sampling)
+                ws = [keep(m.weight.detach()) for m in d.gaussian_kernels]
+                modes = [m.padding_mode for m in d.gaussian_kernels]
+                out[f"blur/{routine}/{sampling}"] = dict(T=T, t=t, ws=ws, modes=modes, q=tensor_digest(d.q_sample(x, t)),
+                                                         sample=walk(d.sample(batch_size=B, img=x)))
+        ref = ref_shim.load("denoising")
+        T, t = 7, torch.tensor([6, 1])
+        e = torch.randn(B, 3, S, S, generator=g)
+        out["noise/e"] = e
+        for sampling in ("x0_step_down", "ddim"):
+            d = ref.GaussianDiffusion(rnet, image_size=S, channels=3, timesteps=T, sampling_routine=sampling)
+            out[f"noise/{sampling}"] = dict(T=T, t=t, q=tensor_digest(d.q_sample(x, e, t)), gen=walk(d.gen_sample(batch_size=B, img=e)),
+                                            sample=walk(d.sample(batch_size=B, img=e)), ca=d.sqrt_alphas_cumprod.clone(),
+                                            cb=d.sqrt_one_minus_alphas_cumprod.clone())
+        ref = ref_shim.load("resolution")
+        for routine, mode in (("Incremental", "bicubic"), ("Incremental_area_factor_2", "area")):
+            T, t = 3, torch.tensor([2, 0])
+            d = ref.GaussianDiffusion(rnet, image_size=S, device_of_kernel="cpu", channels=3, timesteps=T, resolution_routine=routine,
+                                      sampling_routine="x0_step_down")
+            out[f"resolution/{routine}"] = dict(T=T, t=t, mode=mode, q=tensor_digest(d.q_sample(x, t)), sample=walk(d.sample(batch_size=B, img=x)))
+        ref = ref_shim.load("defading")
+        for routine in ("Incremental", "Constant"):
+            for sampling in ("default", "x0_step_down"):
+                T, t = 5, torch.tensor([4, 1])
+                d = ref.GaussianDiffusion(rnet, image_size=S, device_of_kernel="cpu", channels=3, timesteps=T, kernel_std=0.4, initial_mask=2,
+                                          fade_routine=routine, sampling_routine=sampling)
+                out[f"fade/{routine}/{sampling}"] = dict(T=T, t=t, masks=keep(d.fade_kernels), q=tensor_digest(d.q_sample(x, t)),
+                                                         sample=walk(d.sample(batch_size=B, faded_recon_sample=x)))
+    return out
+
+
+def tensor_digest(t):
+    """sha256 over a tensor's dtype, shape and bytes: equal digests <=> torch.equal (and the same dtype)."""
+    import hashlib
+    t = t.detach().cpu().contiguous()
+    h = hashlib.sha256(("%s %s;" % (t.dtype, tuple(t.shape))).encode())
+    h.update(t.numpy().tobytes())
+    return h.hexdigest()
+
+
+def bitexact_cases():
+    """The reference side of tests/test_oracle.py::test_oracle_bit_exact_vs_live_reference, same seeds and calls: a Unet(dim=8,
+    (1, 2, 4, 8), channels=1) at 32 x 32 and a Model(ch=32, (1, 2, 2), 2 res blocks, attention at 8) at 16 x 16 -> live_bitexact.pt.
+    The 10 MB of seeded initial weights are not stored, only their sd_digest: the test redraws them from the same seed."""
+    ref = ref_shim.load("deblurring")
+    torch.manual_seed(7)
+    net = ref.Unet(dim=8, dim_mults=(1, 2, 4, 8), channels=1)
+    x, t = torch.randn(2, 1, 32, 32), torch.tensor([5, 11])
+    with torch.no_grad():
+        unet = dict(sd_sha256=sd_digest(net.state_dict()), x=x, t=t, y=net(x, t))
+    m = ref.Model(resolution=16, in_channels=3, out_ch=3, ch=32, ch_mult=(1, 2, 2), num_res_blocks=2, attn_resolutions=(8,), dropout=0.1).eval()
+    x = torch.randn(2, 3, 16, 16)
+    with torch.no_grad():
+        model = dict(sd_sha256=sd_digest(m.state_dict()), x=x, t=t, y=m(x, t))
+    return {"unet": unet, "model": model}
+
+
+def sd_digest(sd):
+    """sha256 over a state dict's names, dtypes, shapes and bytes, in its order."""
+    import hashlib
+    h = hashlib.sha256()
+    for k, v in sd.items():
+        v = v.detach().cpu().contiguous()
+        h.update(("%s %s %s;" % (k, v.dtype, tuple(v.shape))).encode())
+        h.update(v.numpy().tobytes())
+    return h.hexdigest()
+
+
+# the classes tests/test_boundary.py compares, per reference package (ref_shim name)
+SIGNATURE_CLASSES = {
+    "deblurring": ("Unet", "Model", "GaussianDiffusion", "Trainer"),
+    "denoising": ("Unet", "GaussianDiffusion", "Trainer"),
+    "resolution": ("Unet", "Model", "GaussianDiffusion", "Trainer"),
+    "defading": ("Unet", "Model", "GaussianDiffusion", "Trainer"),
+    "demixing": ("Unet", "GaussianDiffusion", "Trainer"),
+    "defading_generation": ("Unet", "GaussianDiffusion", "Trainer"),
+}
+
+
+def own_methods(cls):
+    """public callables the class itself (not nn.Module / object) defines, plus __init__ and forward"""
+    out = {}
+    for klass in cls.__mro__:
+        if klass.__module__.startswith("torch") or klass is object:
+            continue
+        for name, v in vars(klass).items():
+            if callable(v) and (not name.startswith("_") or name == "__init__") and name not in out:
+                out[name] = v
+    return out
+
+
+def signature_params(fn):
+    """[[name, kind, default]] of a callable: kind = inspect.Parameter kind name, default = repr() of it, None when there is none."""
+    import inspect
+    return [[p.name, p.kind.name, None if p.default is inspect.Parameter.empty else repr(p.default)]
+            for p in inspect.signature(fn).parameters.values()]
+
+
+def signature_case(which):
+    """{class: {method: [[name, kind, default repr]]}} of every public method one reference package defines on its exported classes."""
+    ref = ref_shim.load(which)
+    return {c: {m: signature_params(fn) for m, fn in sorted(own_methods(getattr(ref, c)).items())} for c in SIGNATURE_CLASSES[which]}
+
+
+def signature_cases():
+    """signature_case() of every package tests/test_boundary.py compares -> reference_signatures.json."""
+    return {which: signature_case(which) for which in SIGNATURE_CLASSES}
+
+
+
+def write_live_cases():
+    """The fixtures that let the live-reference tests run where the reference tree is absent."""
+    import json
+    torch.save(sampler_cases(), os.path.join(HERE, "live_samplers.pt"))
+    torch.save(bitexact_cases(), os.path.join(HERE, "live_bitexact.pt"))
+    with open(os.path.join(HERE, "reference_signatures.json"), "w") as f:
+        json.dump(signature_cases(), f, indent=1, sort_keys=True)
+        f.write("\n")
+    for f in ("live_samplers.pt", "live_bitexact.pt", "reference_signatures.json"):
+        print(f, os.path.getsize(os.path.join(HERE, f)) // 1024, "KiB")
+
+
 def main():
     assert ref_shim.available(), "needs /root/reference (build container)"
+    if "--live" in sys.argv:                                          # only (re)write live_samplers.pt, live_bitexact.pt, reference_signatures.json
+        write_live_cases()
+        return
     if "--mixing" in sys.argv:                                        # only (re)write mixing.pt
         sd = torch.load(os.path.join(HERE, "diffusion.pt"), weights_only=False)["deblur/net_sd"]
         torch.save(mixing_cases(sd), os.path.join(HERE, "mixing.pt"))
@@ -522,6 +671,7 @@ def main():
     torch.save(extra_cases(dc["deblur/net_sd"]), os.path.join(HERE, "extras.pt"))
     torch.save(evaluation_cases(dc["deblur/net_sd"]), os.path.join(HERE, "evaluation.pt"))
     torch.save(fullsize_cases(dc["deblur/net_sd"]), os.path.join(HERE, "fullsize.pt"))
+    write_live_cases()
     # torchgeometry boundary: values observed when the reference builds its kernels through the shim
     k = ref_shim.get_gaussian_kernel2d((11, 11), (7.0, 7.0))
     print("k=11 sigma=7 centre %.10f corner %.10f" % (k[5, 5].item(), k[0, 0].item()))

@@ -25,7 +25,7 @@ def _free_port():
 def test_bench_two_ranks_json_line():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--batch", "8", "--no-sample", "--no-secondary", "--no-cpu-baseline"]
+           "--batch", "8", "--full", "--no-sample", "--no-secondary", "--no-cpu-baseline"]
     env = dict(os.environ, COLDDIFF_DIST_BACKEND="gloo", COLDDIFF_SHARE_GPU="1")
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=REPO)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
@@ -38,6 +38,37 @@ def test_bench_two_ranks_json_line():
     gx = out["gradient_exchange"]
     assert gx["buckets"] >= 6 and gx["bytes_per_step"] >= 4 * 56_615_708 and gx["allreduce_ms_per_step"] > 0
     assert "roofline" in out and out["roofline"]["frac"] > 0
+
+
+@pytest.mark.gpu
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain run (no --full) prints the headline line only, with --steps timed steps behind `ms_per_step`, and --dump-outputs writes
+    the last timed step's loss and the seeded state samples as float32 / float64 .npy files, 64 MB at most in all."""
+    import numpy as np
+    out_dir = tmp_path / "outputs"
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "8",
+           "--dump-outputs", str(out_dir)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=REPO,
+                       env={k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")})
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    out = json.loads(lines[0])
+    assert out["metric"] == "unet_train_imgs_per_sec" and out["unit"] == "img/s" and out["higher_is_better"] is True and out["dtype"]
+    assert out["steps"] == 3 and out["warmup"] == 1 and out["ms_per_step"] > 0
+    assert abs(out["value"] - 2 * 8 / (out["ms_per_step"] * 1e-3)) <= 0.01 * out["value"]
+    for extra in ("roofline", "gemm_kernels", "cpu_baseline", "secondary", "bf16_mode", "sample_ms_per_img_200step", "selfcheck"):
+        assert extra not in out, extra
+    files = sorted(p.name for p in out_dir.iterdir())
+    assert files == sorted(["loss.npy", "params_sample.npy", "adam_exp_avg_sample.npy", "adam_exp_avg_sq_sample.npy", "ema_params_sample.npy",
+                            "sample_index.npy"])
+    assert sum(p.stat().st_size for p in out_dir.iterdir()) <= 64 << 20
+    arrays = {f[:-4]: np.load(out_dir / f) for f in files}
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+    assert arrays["loss"].shape == (1,) and np.isfinite(arrays["loss"]).all() and arrays["loss"][0] > 0
+    n = arrays["sample_index"].shape[0]
+    assert n > 0 and all(arrays[k].shape == (n,) for k in arrays if k.endswith("_sample"))
+    assert np.isfinite(arrays["params_sample"]).all() and (arrays["adam_exp_avg_sq_sample"] >= 0).all()
 
 
 def test_bench_refuses_a_mismatched_world():

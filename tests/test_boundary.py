@@ -1,4 +1,6 @@
-"""The drop-in boundary, checked against the LIVE reference (build container only: /root/reference does not exist on the GPU box).
+"""The drop-in boundary, checked against the reference's signatures: LIVE where the reference tree exists (the build container), and
+everywhere against tests/golden/reference_signatures.json, which tests/golden/make_golden.py records from it (and which the live run
+requires to be equal to what it reads).
 
 The reference has no FFI; its boundary for the hot path is the Python class API of its packages.  Here every exported class
 of every package and every public method the reference defines on it is compared by `inspect.signature` with the class of the same name in
@@ -11,6 +13,7 @@ load_path=, dataset='mnist')).
 """
 import importlib
 import inspect
+import json
 import os
 import sys
 
@@ -18,9 +21,8 @@ import pytest
 
 from oracle import ref_shim
 
-pytestmark = pytest.mark.skipif(not ref_shim.available(), reason="the reference tree only exists in the build container")
-
 PKG = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "cold-diffusion-models_amd")
+GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 # reference package (ref_shim name) -> (import path of the drop-in package, exported classes)
 PACKAGES = {
@@ -48,63 +50,74 @@ def _mine(name):
     return importlib.import_module(name)
 
 
-def _params(fn):
-    return [(p.name, p.kind, p.default) for p in inspect.signature(fn).parameters.values()]
+def _golden():
+    sys.path.insert(0, GOLD)
+    try:
+        import make_golden
+    finally:
+        sys.path.remove(GOLD)
+    return make_golden
 
 
-def _accepts_every_reference_call(rfn, mfn):
-    r, m = _params(rfn), _params(mfn)
+def _reference_signatures(which):
+    """{class: {method: [[name, kind, default repr]]}} of one reference package: the recording, equal to the live reference's where
+    the tree exists."""
+    with open(os.path.join(GOLD, "reference_signatures.json")) as f:
+        recorded = json.load(f)[which]
+    if ref_shim.available():
+        assert _golden().signature_case(which) == recorded, "tests/golden/reference_signatures.json is stale: make_golden.py --live"
+    return recorded
+
+
+# a parameter as make_golden.signature_params records it: [name, kind name, repr(default) or None when it has none]
+_VAR = ("VAR_POSITIONAL", "VAR_KEYWORD")
+
+
+def _accepts_every_reference_call(r, m):
     if len(m) < len(r):
         return False
     for (rn, rk, rd), (mn, mk, md) in zip(r, m):
         if rn != mn or rk != mk:
             return False
-        if rd is not inspect.Parameter.empty and rd != md:      # same default wherever the reference has one
+        if rd is not None and rd != md:      # same default wherever the reference has one
             return False
-    return all(md is not inspect.Parameter.empty or mk in (inspect.Parameter.VAR_POSITIONAL, inspect.Parameter.VAR_KEYWORD) for _, mk, md in m[len(r):])
+    return all(md is not None or mk in _VAR for _, mk, md in m[len(r):])
 
 
-def _forwards_keywords(rfn, mfn):
+def _forwards_keywords(rp, m):
     """A constructor written as (self, <the reference's positional parameters>, *, <some of its keywords>, **kw) that hands **kw to a base
     class of this repository: it accepts the reference's calls iff its named parameters agree with the reference's of the same name."""
-    r = {n: (k, d) for n, k, d in _params(rfn)}
-    m = _params(mfn)
-    if not any(k == inspect.Parameter.VAR_KEYWORD for _, k, _ in m):
+    r = {n: (k, d) for n, k, d in rp}
+    if not any(k == "VAR_KEYWORD" for _, k, _ in m):
         return False
-    pos_r = [n for n, k, _ in _params(rfn) if k == inspect.Parameter.POSITIONAL_OR_KEYWORD]
-    pos_m = [n for n, k, _ in m if k == inspect.Parameter.POSITIONAL_OR_KEYWORD]
+    pos_r = [n for n, k, _ in rp if k == "POSITIONAL_OR_KEYWORD"]
+    pos_m = [n for n, k, _ in m if k == "POSITIONAL_OR_KEYWORD"]
     if pos_m != pos_r:
         return False
-    return all(n not in r or r[n] == (k, d) for n, k, d in m if k == inspect.Parameter.KEYWORD_ONLY)
+    return all(n not in r or r[n] == (k, d) for n, k, d in m if k == "KEYWORD_ONLY")
 
 
-def _own_methods(cls):
-    """public callables the class itself (not nn.Module / object) defines, plus __init__ and forward"""
-    out = {}
-    for klass in cls.__mro__:
-        if klass.__module__.startswith("torch") or klass is object:
-            continue
-        for name, v in vars(klass).items():
-            if callable(v) and (not name.startswith("_") or name == "__init__") and name not in out:
-                out[name] = v
-    return out
+def _shown(params):
+    return "(" + ", ".join(n if d is None else "%s=%s" % (n, d) for n, _, d in params) + ")"
 
 
 @pytest.mark.parametrize("which", sorted(PACKAGES))
 def test_signatures_equal_the_live_reference(which):
-    ref = ref_shim.load(which)
+    M = _golden()
+    ref = _reference_signatures(which)
     mine = _mine(PACKAGES[which][0])
     missing, different, optional = [], [], []
+    assert set(ref) == set(PACKAGES[which][1]) and M.SIGNATURE_CLASSES[which] == PACKAGES[which][1]
     for cname in PACKAGES[which][1]:
-        rc, mc = getattr(ref, cname), getattr(mine, cname)
-        mm = _own_methods(mc)
-        for mname, rfn in _own_methods(rc).items():
+        mc = getattr(mine, cname)
+        mm = M.own_methods(mc)
+        for mname, rparams in ref[cname].items():
             if mname not in mm and not hasattr(mc, mname):
                 (optional if (cname == "Trainer" and mname not in TRAINER_REQUIRED) else missing).append(cname + "." + mname)
                 continue
-            mfn = mm.get(mname, getattr(mc, mname))
-            if not (_accepts_every_reference_call(rfn, mfn) or (mname == "__init__" and _forwards_keywords(rfn, mfn))):
-                different.append((cname + "." + mname, str(inspect.signature(rfn)), str(inspect.signature(mfn))))
+            mparams = M.signature_params(mm.get(mname, getattr(mc, mname)))
+            if not (_accepts_every_reference_call(rparams, mparams) or (mname == "__init__" and _forwards_keywords(rparams, mparams))):
+                different.append((cname + "." + mname, _shown(rparams), _shown(mparams)))
     print(which, "- figure methods of the reference Trainer that are not built:", optional)
     assert {o.split(".")[1] for o in optional} <= FIGURE_CODE, "Trainer methods without a counterpart that are not figure code: %s" % optional
     assert not missing, "reference methods without a counterpart: %s" % missing

@@ -1,7 +1,8 @@
 """The CPU oracle (oracle/cold_oracle.py) is pinned against the reference itself:
   * always: against the committed golden vectors the unmodified reference produced
     (tests/golden/make_golden.py), and the torchgeometry probe values recorded in SURVEY.md §8(c)
-  * in the build container (where /root/reference exists): live, bit-for-bit on CPU.
+  * in the build container (where the reference tree exists): live, bit-for-bit on CPU; elsewhere the live tests check the oracle
+    against what make_golden.py recorded from the same reference calls (live_samplers.pt, live_bitexact.pt).
 """
 import os
 
@@ -264,13 +265,15 @@ def test_make_golden_regenerates_every_committed_fixture():
         _regenerate_and_compare(M)
     finally:
         torch.set_num_threads(threads)
-    made = {"unet_dim8.pt", "model_ch32.pt", "model_noconv.pt", "diffusion.pt", "variants.pt", "mixing.pt", "extras.pt", "evaluation.pt", "fullsize.pt"}
-    assert made == {f for f in os.listdir(GOLD) if f.endswith(".pt")}          # no fixture without a generator
+    made = {"unet_dim8.pt", "model_ch32.pt", "model_noconv.pt", "diffusion.pt", "variants.pt", "mixing.pt", "extras.pt", "evaluation.pt", "fullsize.pt",
+            "live_samplers.pt", "live_bitexact.pt", "reference_signatures.json"}
+    assert made == {f for f in os.listdir(GOLD) if f.endswith((".pt", ".json"))}          # no fixture without a generator
 
 
 def _regenerate_and_compare(M):
     import contextlib
     import io
+    import json
     with contextlib.redirect_stdout(io.StringIO()):
         ref = ref_shim.load("deblurring")
         _same(M.unet_case(ref), load("unet_dim8.pt"), "unet_dim8")
@@ -284,13 +287,80 @@ def _regenerate_and_compare(M):
         _same(M.extra_cases(sd), load("extras.pt"), "extras")
         _same(M.evaluation_cases(sd), load("evaluation.pt"), "evaluation")
         _same(M.fullsize_cases(sd), load("fullsize.pt"), "fullsize")
+        _same(M.sampler_cases(), load("live_samplers.pt"), "live_samplers")
+        _same(M.bitexact_cases(), load("live_bitexact.pt"), "live_bitexact")
+        with open(os.path.join(GOLD, "reference_signatures.json")) as f:
+            _same(M.signature_cases(), json.load(f), "reference_signatures")
 
 
-@pytest.mark.skipif(not ref_shim.available(), reason="reference tree only exists in the build container")
 def test_oracle_vs_live_reference_degradations_and_samplers():
-    """q_sample + sample of the four packages, live against the imported reference at a size and schedule no fixture holds
+    """q_sample + sample of the four packages, live against the imported reference at a size and schedule no other fixture holds
     (24 x 24, its own seeds): blur (DEBLUR:393-455, 927-960), noise (DENOISE:342-434, 517-522), pixelation (RESOL:417-459, 630-652),
-    fading (DEFADE:354-425, 496-535)."""
+    fading (DEFADE:354-425, 496-535).  Without the reference tree: against live_samplers.pt, the same reference calls recorded."""
+    if ref_shim.available():
+        _live_degradations_and_samplers()
+    _recorded_degradations_and_samplers()
+
+
+def _recorded_degradations_and_samplers():
+    # network outputs to 1e-6 (as the other golden tests): the recording host's CPU convolutions sum in another order at another thread
+    # count (<= 3.5e-7 seen); everything without a network in it stays bit-exact (the fixture holds those as make_golden.tensor_digest)
+    import contextlib
+    import io
+    import sys
+    sys.path.insert(0, GOLD)
+    try:
+        import make_golden as M
+    finally:
+        sys.path.remove(GOLD)
+    from deblurring_diffusion_pytorch import Unet
+    g = load("live_samplers.pt")
+    x = g["x"]
+    B, S = x.shape[0], x.shape[-1]
+    torch.manual_seed(99)                                 # the reference's weights, redrawn from its seed: they must hash to what it drew
+    with contextlib.redirect_stdout(io.StringIO()):
+        sd = Unet(dim=8, dim_mults=(1, 2), channels=3).state_dict()
+    assert M.sd_digest(sd) == g["sd_sha256"]
+    same = lambda digest, t: digest == M.tensor_digest(t)             # torch.equal against the reference's tensor
+    net = lambda im, st: O.unet_forward(sd, im, st)
+    with torch.no_grad():
+        for key, c in g.items():
+            if key.startswith("blur/"):
+                ws, modes, T = c["ws"], c["modes"], c["T"]
+                assert same(c["q"], O.blur_q_sample(x, c["t"], ws, modes, T)), key
+                xt, direct, img = c["sample"]
+                oxt, odirect, oimg = O.cold_sample(net, lambda z, i: O.blur_step(z, ws[i], modes[i]), x, T, key.split("/")[2])
+                assert same(xt, oxt) and (direct - odirect).abs().max() <= 1e-6 and (img - oimg).abs().max() <= 1e-6, key
+            elif key.startswith("noise/") and key != "noise/e":
+                e, T, sampling = g["noise/e"], c["T"], key.split("/")[1]
+                own = O.cosine_tables(T)            # (torch.cos: an ulp apart between CPU vector ISAs; the chain runs on the reference's tables)
+                assert max((u - v).abs().max().item() for u, v in zip(own, (c["ca"], c["cb"]))) <= 2.4e-7, key
+                ca, cb = c["ca"], c["cb"]
+                assert same(c["q"], O.noise_q_sample(x, e, c["t"], ca, cb)), key
+                for got, want in ((c["gen"], O.noise_sample(net, e, T, ca, cb, fixed_noise=sampling == "x0_step_down")),
+                                  (c["sample"], O.noise_sample(net, e, T, ca, cb, fixed_noise=False))):
+                    assert same(got[0], want[0]) and (got[1] - want[1]).abs().max() <= 1e-6 and (got[2] - want[2]).abs().max() <= 2e-6, key
+            elif key.startswith("resolution/"):
+                T, mode = c["T"], c["mode"]
+                sizes = O.pixelate_sizes(key.split("/")[1], T, S)
+                assert same(c["q"], O.pixelate_q_sample(x, c["t"], sizes, mode)), key
+                xt, direct, img = c["sample"]
+                oxt, odirect, oimg = O.cold_sample(net, lambda z, i: O.pixelate_step(z, sizes[i], mode), x, T, "x0_step_down")
+                assert same(xt, oxt) and (direct - odirect).abs().max() <= 1e-6 and (img - oimg).abs().max() <= 1e-6, key
+            elif key.startswith("fade/"):
+                _, routine, sampling = key.split("/")
+                T = c["T"]
+                own = O.fade_kernels(routine, T, S, 0.4, 2)        # (torch.exp: as above, test_fullsize_random_fade_matches_golden)
+                assert (own - c["masks"]).abs().max() <= 2.4e-7, key
+                masks = c["masks"]
+                assert same(c["q"], O.fade_q_sample(x, c["t"], masks)), key
+                xt, direct, img = c["sample"]
+                oxt, odirect, oimg = O.cold_sample(net, lambda z, i: masks[i] * z, x, T, sampling)
+                assert same(xt, oxt) and (direct - odirect).abs().max() <= 1e-6 and (img - oimg).abs().max() <= 1e-6, key
+    assert B == 2 and sum(k.startswith(("blur/", "noise/x", "noise/d", "resolution/", "fade/")) for k in g) == 4 + 2 + 2 + 4
+
+
+def _live_degradations_and_samplers():
     import contextlib
     import io
     S, B = 24, 2
@@ -354,8 +424,41 @@ def test_oracle_vs_live_reference_degradations_and_samplers():
                 assert torch.equal(xt, oxt) and torch.equal(direct, odirect) and (img - oimg).abs().max() <= 1e-6
 
 
-@pytest.mark.skipif(not ref_shim.available(), reason="reference tree only exists in the build container")
 def test_oracle_bit_exact_vs_live_reference():
+    """Unet and Model forwards of the oracle against the reference's, live where the reference tree exists; everywhere against
+    live_bitexact.pt (the same reference calls recorded; the seeded weights are redrawn here and must hash to what the reference drew)."""
+    if ref_shim.available():
+        _live_bit_exact()
+    _recorded_bit_exact()
+
+
+def _recorded_bit_exact():
+    import contextlib
+    import io
+    import sys
+    sys.path.insert(0, GOLD)
+    try:
+        import make_golden as M
+    finally:
+        sys.path.remove(GOLD)
+    from deblurring_diffusion_pytorch import Model, Unet
+    g = load("live_bitexact.pt")
+    torch.manual_seed(7)                                  # the draws of bitexact_cases(): weights, then inputs, in the same order
+    with contextlib.redirect_stdout(io.StringIO()):
+        sd = Unet(dim=8, dim_mults=(1, 2, 4, 8), channels=1).state_dict()
+    assert M.sd_digest(sd) == g["unet"]["sd_sha256"]
+    assert torch.equal(torch.randn(2, 1, 32, 32), g["unet"]["x"])
+    with torch.no_grad():
+        assert (g["unet"]["y"] - O.unet_forward(sd, g["unet"]["x"], g["unet"]["t"])).abs().max() <= 1e-6      # (thread count: see above)
+    sd = Model(resolution=16, in_channels=3, out_ch=3, ch=32, ch_mult=(1, 2, 2), num_res_blocks=2, attn_resolutions=(8,), dropout=0.1).state_dict()
+    assert M.sd_digest(sd) == g["model"]["sd_sha256"]
+    assert torch.equal(torch.randn(2, 3, 16, 16), g["model"]["x"])
+    with torch.no_grad():
+        y = O.model_forward(sd, g["model"]["x"], g["model"]["t"], num_res_blocks=2, num_resolutions=3)
+    assert (g["model"]["y"] - y).abs().max() <= 2e-6 * max(1.0, g["model"]["y"].abs().max().item())     # (<= 1.4e-6 seen on one thread)
+
+
+def _live_bit_exact():
     ref = ref_shim.load("deblurring")
     torch.manual_seed(7)
     net = ref.Unet(dim=8, dim_mults=(1, 2, 4, 8), channels=1)
