@@ -588,8 +588,9 @@ static int dwconv7_entry(const void* x, int ldx, const float* w, int ldw, const 
     const int Cp = (C + 3) & ~3;
     CDF_REQUIRE(ldx % 4 == 0 && ldy % 4 == 0 && ldw % 4 == 0 && ldx >= Cp && ldy >= Cp && ldw >= Cp, "cdf_dwconv7: pitches must be multiples of 4 and >= roundup4(C)");
     CDF_REQUIRE(!bias || (C % 4 == 0), "cdf_dwconv7: bias with C %% 4 != 0 needs a padded bias (pass a padded vector and C rounded up)");
-    {   // the kernel's per-image element offsets are 24 x 24-bit products kept in 32 bits
-        const long long ldmax = ldx > ldy ? (ldx > ldr ? ldx : ldr) : (ldy > ldr ? ldy : ldr);
+    {   // the kernel's per-image element offsets are 24 x 24-bit products kept in 32 bits (the bf16 planes' pitch ld_ys included)
+        long long ldmax = ldx > ldy ? (ldx > ldr ? ldx : ldr) : (ldy > ldr ? ldy : ldr);
+        if (y_hi && ld_ys > ldmax) ldmax = ld_ys;
         CDF_REQUIRE((long long)H * W < (1 << 24) && ldmax < (1 << 24) && (long long)H * W * ldmax < (1LL << 30),
                     "cdf_dwconv7: image of %d x %d pixels at pitch %lld is beyond the kernel's 32-bit per-image offsets", H, W, ldmax);
     }

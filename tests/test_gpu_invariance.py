@@ -1,0 +1,279 @@
+"""Run-to-run invariance on the MI355X: the library uses no atomics, sums its split-K slabs and partial sums in a fixed order and
+promises bit-identical results for identical inputs (data-parallel replicas stay bit-identical).  The simulator runs one
+lane at a time, so a missing barrier or an LDS write-after-read hazard can only show here.  Every check compares with torch.equal:
+  * the benchmark's fused 64-image step at 128 x 128, twice (bf16x3 and bf16 modes), once more on NaN-poisoned allocations, and once
+    with the resident row-halo grid every multi-rank step launches (resident_reserve = 32);
+  * the sampler at B = 16, 128 x 128 (5 reverse steps) and BASELINE config 2's network at 32 x 32, B = 128: twice and under poison;
+  * a coverage guard: every cdf_* entry point the bench step and a sampler step call must name its production-shape test below.
+"""
+import contextlib
+import io
+
+import pytest
+import torch
+
+from poison import poisoned_allocations
+from test_gpu_parity2 import _fused_bench_step, bench_step_inputs
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+
+
+def quiet(fn, *a, **k):
+    with contextlib.redirect_stdout(io.StringIO()):
+        return fn(*a, **k)
+
+
+class Recorder:
+    """Wraps every cdf_* attribute of the loaded library (the way bench.py's GemmTimer wraps the GEMM entry points) and records
+    the name and arguments of each call while active."""
+
+    def __init__(self, lib):
+        self.lib, self.calls, self.orig = lib, [], {}
+
+    def __enter__(self):
+        for name in list(vars(self.lib)):
+            if name.startswith("cdf_"):
+                fn = self.orig[name] = getattr(self.lib, name)
+                setattr(self.lib, name, (lambda n, f: lambda *a: (self.calls.append((n, a)), f(*a))[1])(name, fn))
+        return self
+
+    def __exit__(self, *exc):
+        for name, fn in self.orig.items():
+            setattr(self.lib, name, fn)
+
+    def names(self):
+        return {n for n, _ in self.calls}
+
+
+@pytest.fixture(scope="module")
+def bench_data():
+    return bench_step_inputs()
+
+
+def _step(f):
+    """loss + every parameter gradient of one fused bench step, on the host."""
+    from colddiff import runtime as rt
+    rt.bump_weights_epoch()
+    tr, net, loss = _fused_bench_step(f)
+    out = [torch.tensor([loss])] + [p.grad.detach().cpu().clone() for p in net.parameters()]
+    del tr, net
+    return out
+
+
+def _same(a, b, what):
+    assert len(a) == len(b)
+    for i, (u, v) in enumerate(zip(a, b)):
+        assert torch.isfinite(u).all(), (what, i)
+        assert torch.equal(u, v), (what, i, (u - v).abs().max().item())
+
+
+@contextlib.contextmanager
+def _reserve(n):
+    from colddiff import runtime as rt
+    saved = rt.tuning().get("resident_reserve")
+    rt.tuning().set(resident_reserve=n)
+    try:
+        yield
+    finally:
+        rt.tuning().set(resident_reserve=saved)
+
+
+@pytest.mark.parametrize("mode", ["bf16x3", "bf16"])
+def test_bench_step_twice_poisoned_and_reserved_bit_identical(bench_data, mode):
+    """The bench step from the same state: twice, then on poisoned allocations, then on the resident grid of a multi-rank step
+    (resident_reserve = 32 CUs left free: fewer resident blocks, each walking more tiles).  Each tile is computed by one block in a
+    fixed K order whatever the grid, so all four must agree bit for bit."""
+    from colddiff import runtime as rt
+    with rt.precision_scope(mode):
+        with _reserve(0):
+            first = _step(bench_data)
+            second = _step(bench_data)
+            with poisoned_allocations():
+                poisoned = _step(bench_data)
+        with _reserve(32):
+            reserved = _step(bench_data)
+    _same(first, second, "second run")
+    _same(first, poisoned, "poisoned run")
+    _same(first, reserved, "resident_reserve=32")
+    print(mode, "bench step: loss", first[0].item(), "-- second run, poisoned run and resident_reserve=32 bit-identical")
+
+
+def _sampler_run(sd, noise):
+    from denoising_diffusion_pytorch import GaussianDiffusion, Unet
+    from colddiff import runtime as rt
+    rt.bump_weights_epoch()
+    net = quiet(Unet, dim=64, dim_mults=(1, 2, 4, 8), channels=3)
+    net.load_state_dict(sd)
+    d = GaussianDiffusion(net.to(DEV), image_size=128, channels=3, timesteps=5, sampling_routine="x0_step_down").to(DEV)
+    with torch.no_grad():
+        out = [v.detach().cpu().clone() for v in quiet(d.gen_sample, batch_size=noise.shape[0], img=noise.to(DEV))]
+    torch.cuda.synchronize()
+    return out
+
+
+def test_sampler_twice_and_poisoned_bit_identical(bench_data):
+    """gen_sample at B = 16, 128 x 128, 5 reverse steps (the sampler's shapes): twice, and once on poisoned allocations."""
+    torch.manual_seed(4)
+    noise = torch.randn(16, 3, 128, 128)
+    first = _sampler_run(bench_data["sd"], noise)
+    second = _sampler_run(bench_data["sd"], noise)
+    with poisoned_allocations():
+        poisoned = _sampler_run(bench_data["sd"], noise)
+    _same(first, second, "second run")
+    _same(first, poisoned, "poisoned run")
+
+
+def test_config2_model_twice_and_poisoned_bit_identical():
+    """BASELINE config 2: Model(ch=128, (1, 2, 2, 2), 2 res blocks, attention at 16 x 16, dropout 0.1) at 32 x 32, B = 128, forward +
+    backward: output, input gradient and every parameter gradient, twice and once on poisoned allocations (the dropout seed is drawn
+    from torch's generator, reseeded per run)."""
+    from deblurring_diffusion_pytorch import Model
+    from colddiff import runtime as rt
+    kw = dict(resolution=32, in_channels=3, out_ch=3, ch=128, ch_mult=(1, 2, 2, 2), num_res_blocks=2, attn_resolutions=(16,), dropout=0.1)
+    torch.manual_seed(21)
+    sd = quiet(Model, **kw).state_dict()
+    x, t, gy = torch.rand(128, 3, 32, 32) * 2 - 1, torch.randint(0, 1000, (128,)), torch.randn(128, 3, 32, 32) / 1000
+
+    def run():
+        rt.bump_weights_epoch()
+        net = Model(**kw)
+        net.load_state_dict(sd)
+        net = net.to(DEV)
+        xd = x.to(DEV).requires_grad_(True)
+        torch.manual_seed(5)
+        y = net(xd, t.to(DEV))
+        y.backward(gy.to(DEV))
+        torch.cuda.synchronize()
+        return [y.detach().cpu(), xd.grad.cpu()] + [p.grad.cpu().clone() for p in net.parameters()]
+    first = run()
+    second = run()
+    with poisoned_allocations():
+        poisoned = run()
+    _same(first, second, "second run")
+    _same(first, poisoned, "poisoned run")
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------
+# coverage guard: every entry point on the hot path names the test(s) that run it at a production shape
+# ------------------------------------------------------------------------------------------------------------------------------------
+_KP = "test_kernels_production.py::"
+_K = "test_kernels.py::"
+_P2 = "test_gpu_parity2.py::"
+_BS = "test_gpu_invariance.py::test_bench_step_twice_poisoned_and_reserved_bit_identical"
+COVERED_AT_PRODUCTION_SHAPE = {
+    # GEMM family: the *_large GPU tests run the shapes the bench / configs launch; the step-level tests above run them in the step
+    "cdf_conv_gemm": [_K + "test_conv_gemm_large", _K + "test_conv_presplit_large"],
+    "cdf_conv_gemm_bf16x": [_K + "test_conv_presplit_large", _K + "test_specialised_epilogue_equals_generic_large"],
+    "cdf_conv_gemm_bf16x_lnbwd": [_K + "test_conv_dgrad_with_layernorm_backward_epilogue_large"],
+    "cdf_conv_wgrad": [_K + "test_conv_gemm_large"],
+    "cdf_conv_wgrad_bf16x": [_K + "test_conv_presplit_large"],
+    "cdf_split_bf16": [_K + "test_conv_presplit_large"],
+    "cdf_bf16x_ksplit": [_K + "test_conv_presplit_large"],
+    "cdf_wgrad_nsplit": [_KP + "test_unpack_reduce_bench_slab_counts"],
+    "cdf_unpack_reduce": [_KP + "test_unpack_reduce_bench_slab_counts", _KP + "test_conv_cin4_first_block"],
+    "cdf_unpack_reduce_bias": [_KP + "test_unpack_reduce_bench_slab_counts"],
+    # image-side block
+    "cdf_conv_cin4_fwd": [_KP + "test_conv_cin4_first_block"],
+    "cdf_conv_cin4_dgrad": [_KP + "test_conv_cin4_first_block"],
+    "cdf_conv_cin4_tapsum3": [_KP + "test_conv_cin4_first_block"],
+    "cdf_conv_cin4_wgrad": [_KP + "test_conv_cin4_first_block"],
+    "cdf_conv_cin4_nchunk": [_KP + "test_conv_cin4_first_block"],
+    "cdf_pack_cin4": [_KP + "test_conv_cin4_first_block"],
+    # reductions, norms, depthwise
+    "cdf_colsum": [_KP + "test_colsum_past_chunk_cap"],
+    "cdf_colsum_io": [_KP + "test_colsum_past_chunk_cap"],
+    "cdf_colsum_nchunk": [_KP + "test_colsum_past_chunk_cap"],
+    "cdf_layernorm_blocks": [_KP + "test_layernorm_production"],
+    "cdf_layernorm_c_fwd": [_KP + "test_layernorm_production"],
+    "cdf_layernorm_c_bwd": [_KP + "test_layernorm_production"],
+    "cdf_layernorm_c_bwd_planes": [_KP + "test_layernorm_production"],
+    "cdf_layernorm_c_fwd_io": [_KP + "test_layernorm_production"],
+    "cdf_layernorm_c_bwd_io": [_KP + "test_layernorm_production"],
+    "cdf_groupnorm_fwd_ex": [_KP + "test_groupnorm_production"],
+    "cdf_groupnorm_bwd_ex": [_KP + "test_groupnorm_production"],
+    "cdf_groupnorm_nchunk": [_KP + "test_groupnorm_production"],
+    "cdf_dwconv7": [_KP + "test_dwconv7_production"],
+    "cdf_dwconv7_planes": [_KP + "test_dwconv7_production"],
+    "cdf_dwconv7_wgrad": [_KP + "test_dwconv7_production"],
+    "cdf_dwconv7_wgrad_nchunk": [_KP + "test_dwconv7_production"],
+    # linear attention
+    "cdf_linattn_nsplit": [_KP + "test_linattn_production"],
+    "cdf_linattn_ws_floats": [_KP + "test_linattn_production"],
+    "cdf_linattn_context": [_KP + "test_linattn_production"],
+    "cdf_linattn_dcontext": [_KP + "test_linattn_production"],
+    "cdf_linattn_bwd_kv": [_KP + "test_linattn_production", _KP + "test_linattn_bwd_kv_planes_production"],
+    "cdf_linattn_softk": [_KP + "test_linattn_production"],
+    "cdf_linattn_dk": [_KP + "test_linattn_production"],
+    # ... and the folded attention block's path, which the bench step takes
+    "cdf_linattn_kvctx": [_KP + "test_linattn_kvctx_production"],
+    "cdf_linattn_kvctx_parts": [_KP + "test_linattn_kvctx_production"],
+    "cdf_linattn_finalize": [_KP + "test_linattn_kvctx_production"],
+    "cdf_linattn_bwd_kv_planes": [_KP + "test_linattn_bwd_kv_planes_production"],
+    "cdf_linattn_dctx_finish": [_KP + "test_linattn_dctx_finish_production"],
+    "cdf_dwconv7_io": [_KP + "test_dwconv7_production"],
+    "cdf_dwconv7_wgrad_io": [_KP + "test_dwconv7_production"],
+    # the typed-operand GEMM entry points of the bf16 stream: cdf_conv_gemm / cdf_conv_gemm_bf16x ARE these entry points with io_bf16 = 0
+    # (same tile walk and split; the flag changes only how operands are loaded and stored), so the *_large tests run their production
+    # shapes; the bf16 step at the bench shape runs the bf16 operands
+    "cdf_conv_gemm_io": [_K + "test_conv_gemm_large", _P2 + "test_bf16_mode_bench_shape_fused_step"],
+    "cdf_conv_gemm_bf16x_io": [_K + "test_conv_presplit_large", _P2 + "test_bf16_mode_bench_shape_fused_step"],
+    # elementwise bf16 -> fp32 widening (exactness: test_bf16_storage.py::test_bf16_to_f32_and_back)
+    "cdf_bf16_to_f32": [_P2 + "test_bf16_mode_bench_shape_fused_step", "test_bf16_storage.py::test_bf16_to_f32_and_back"],
+    # GEMM-class entry points in the plain bf16 arithmetic
+    "cdf_conv_gemm_bf16": [_K + "test_conv_gemm_bf16_large"],
+    "cdf_conv_wgrad_bf16": [_K + "test_conv_gemm_bf16_large"],
+    # elementwise and layout operations (no reduction, tile walk or chunk clamp that depends on the shape): the bench-shape step
+    **{n: [_P2 + "test_bench_shape_fused_step_vs_oracle", _BS] for n in (
+        "cdf_act_fwd", "cdf_act_bwd", "cdf_loss_fwd", "cdf_loss_bwd", "cdf_nchw_to_nhwc", "cdf_nhwc_to_nchw", "cdf_noise_qsample",
+        "cdf_sinusoidal", "cdf_linear_small", "cdf_linear_small_wgrad", "cdf_pack_weight", "cdf_pack_weight_bf16")},
+    "cdf_noise_step": ["test_gpu_fullsize.py::test_sampler_full_T_denoise", "test_gpu_invariance.py::test_sampler_twice_and_poisoned_bit_identical"],
+}
+# entry points with nothing shape-dependent to test at scale, with the reason
+EXEMPT = {
+    "cdf_last_error": "host-side error string",
+    "cdf_zero": "memset-class fill; no reduction, tiling or chunk clamp",
+    "cdf_gemm_tuning_default": "host-side defaults of the tuning struct",
+    "cdf_abi_version": "host-side query",
+    "cdf_is_device_build": "host-side query",
+    "cdf_conv_gemm_bf16x_ksplit": "host-side query (split count)",
+    "cdf_conv_gemm_bf16x_lnbwd_ok": "host-side query (epilogue eligibility)",
+    "cdf_conv_wgrad_bf16x_is_row3": "host-side query (kernel form)",
+}
+
+
+def _guard_calls(bench_data):
+    """Every cdf_* call of one bench step in each arithmetic mode the bench reports (bf16x3, and bf16 with its bf16 activation
+    stream) and of one sampler step: (set of names, the (nsplit, T, R, C) of the bf16x3 step's slab reductions)."""
+    from colddiff import runtime as rt
+    names, unpack = set(), set()
+    for mode in ("bf16x3", "bf16"):
+        with rt.precision_scope(mode), Recorder(rt.lib()) as rec:
+            _step(bench_data)
+        names |= rec.names()
+        if mode == "bf16x3":
+            unpack = {tuple(a[2:6]) for n, a in rec.calls if n in ("cdf_unpack_reduce", "cdf_unpack_reduce_bias")}
+    torch.manual_seed(4)
+    with Recorder(rt.lib()) as rec:
+        _sampler_run(bench_data["sd"], torch.randn(16, 3, 128, 128))
+    return names | rec.names(), unpack
+
+
+def test_coverage_guard(bench_data):
+    """A new entry point cannot reach the hot path without a test at a production shape: each name one bench step (both modes) and one
+    sampler step call must be listed above (or exempt, with a reason), and each listed test must exist.  The slab counts
+    test_kernels_production.BENCH_UNPACK tests must still be ones the bench step launches (stale shapes fail here)."""
+    import os
+    import re
+    from test_kernels_production import BENCH_UNPACK
+    names, unpack = _guard_calls(bench_data)
+    here = os.path.dirname(os.path.abspath(__file__))
+    for name, tests in COVERED_AT_PRODUCTION_SHAPE.items():
+        for t in tests:
+            mod, fn = t.split("::")
+            assert re.search(r"^def %s\(" % fn, open(os.path.join(here, mod)).read(), flags=re.M), (name, t)
+    missing = sorted(n for n in names if n not in COVERED_AT_PRODUCTION_SHAPE and n not in EXEMPT)
+    print("entry points called by one bench step (bf16x3, bf16) + one sampler step:", sorted(names))
+    assert not missing, "hot-path entry points without a production-shape test: %s" % missing
+    stale = sorted(set(BENCH_UNPACK) - unpack)
+    assert not stale, "BENCH_UNPACK shapes the bench step no longer launches: %s (it launches %s)" % (stale, sorted(unpack))

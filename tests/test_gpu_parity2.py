@@ -61,13 +61,9 @@ def test_cfg1_unet_one_channel_32():
 BENCH_B, BENCH_ACC, BENCH_T = 32, 2, 200     # bench.py's optimizer step: gradient_accumulate_every = 2 micro-batches of 32 images
 
 
-@pytest.fixture(scope="module")
-def bench_step_oracle():
-    """The oracle side of the step bench.py times, computed ONCE for the bf16x3 and the bf16 test (a thread, so the CPU works while
-    the MI355X does): the reference's optimizer-step semantics (DEBLUR:1188-1195) -- two micro-batches of 32, (loss_i / 2).backward()
-    each -- i.e. loss = mean of the two micro-batch losses, gradient = the sum of both backward passes; 16 chunks of 4 images
-    (gradients of a mean are additive over samples)."""
-    from concurrent.futures import ThreadPoolExecutor
+def bench_step_inputs():
+    """The state and the data / noise / t draws of the bench-shape step (shared by the oracle comparison here and the run-to-run
+    invariance tests of test_gpu_invariance.py)."""
     from denoising_diffusion_pytorch import Unet
     torch.manual_seed(123457)
     net = quiet(Unet, dim=64, dim_mults=(1, 2, 4, 8), channels=3)
@@ -77,6 +73,18 @@ def bench_step_oracle():
     x = torch.randint(0, 256, (n, 3, 128, 128), generator=g).float() / 255 * 2 - 1
     e = torch.randn(n, 3, 128, 128, generator=g)
     t = torch.randint(0, BENCH_T, (n,), generator=g)
+    return {"sd": sd, "x": x, "e": e, "t": t}
+
+
+@pytest.fixture(scope="module")
+def bench_step_oracle():
+    """The oracle side of the step bench.py times, computed ONCE for the bf16x3 and the bf16 test (a thread, so the CPU works while
+    the MI355X does): the reference's optimizer-step semantics (DEBLUR:1188-1195) -- two micro-batches of 32, (loss_i / 2).backward()
+    each -- i.e. loss = mean of the two micro-batch losses, gradient = the sum of both backward passes; 16 chunks of 4 images
+    (gradients of a mean are additive over samples)."""
+    from concurrent.futures import ThreadPoolExecutor
+    f = bench_step_inputs()
+    sd, x, e, t = f["sd"], f["x"], f["e"], f["t"]
 
     def run():
         ca, cb = O.cosine_tables(BENCH_T)
