@@ -283,8 +283,22 @@ static inline int cdf_num_cus() {                                     // CUs of 
 }
 
 
+// ---- plan-only dispatch (cdf_conv_gemm_bf16x_form / cdf_conv_wgrad_bf16x_form, include/colddiff.h) ------------------------------------------------
+// The form queries run the dispatchers themselves: every launcher that is handed a CdfPlan records the kernel it was about to launch (the
+// code colddiff.h documents, its tile count and its grid) and returns before CDF_LAUNCH.  There is no second copy of the conditions.
+struct CdfPlan {
+    int code, tiles, grid;
+};
+enum { CDF_FORM_ROWHALO = 1, CDF_FORM_HALO = 2, CDF_FORM_SPX = 3, CDF_FORM_WGRAD_ROW3 = 1, CDF_FORM_WGRAD_SPX = 2, CDF_FORM_WGRAD_STACK2 = 3 };
+static inline int cdf_plan_set(CdfPlan* p, int form, int bm, int bn, int stages, int ksplit, int w, long long tiles, long long grid) {
+    p->code = form << 24 | (bm / 64) << 20 | (bn / 64) << 16 | stages << 12 | ksplit << 4 | (w / 16);
+    p->tiles = (int)tiles;
+    p->grid = (int)grid;
+    return CDF_OK;
+}
+
 // ---- cross-unit launchers (one plain function per kernel family; the template dispatch lives next to the kernels) --------------------------------
 // halo kernel: W in {16, 32, 64, 128}, n64: 64-wide N tiles, bm: 128 or 256 pixel rows per tile (the caller has checked that the geometry fits)
-int cdf_launch_igemm_halo(int ns, int W, bool n64, int bm, const SpxArgs& a, int M, hipStream_t s);
+int cdf_launch_igemm_halo(int ns, int W, bool n64, int bm, const SpxArgs& a, int M, hipStream_t s, CdfPlan* plan = nullptr);
 // resident row-halo stream kernel; returns CDF_E_UNSUPPORTED when this build has no instance for W (the caller then falls through)
-int cdf_launch_igemm_rowhalo(int ns, int W, bool n64, const SpxArgs& a, int M, hipStream_t s, int reserve);
+int cdf_launch_igemm_rowhalo(int ns, int W, bool n64, const SpxArgs& a, int M, hipStream_t s, int reserve, CdfPlan* plan = nullptr);

@@ -220,7 +220,7 @@ __global__ void __launch_bounds__(512, 1) conv_igemm_halo_kernel(SpxArgs a) {
 }
 
 template <int NS, int W, int BN, int BM>
-static int launch_igemm_halo(const SpxArgs& a, int M, hipStream_t s) {
+static int launch_igemm_halo(const SpxArgs& a, int M, hipStream_t s, CdfPlan* plan) {
     // weight stages: as many as fit next to the two halo buffers
     constexpr int TH = BM / W, HR = (TH + 2) * (W + 2), HRP = (HR + 15) / 16 * 16;
     constexpr size_t abytes = (size_t)2 * 2 * HRP * 64, bstage = (size_t)2 * BN * 64;
@@ -231,26 +231,27 @@ static int launch_igemm_halo(const SpxArgs& a, int M, hipStream_t s) {
     constexpr size_t epi = (size_t)BM * (BN + 8) * sizeof(float);
     constexpr size_t lds = stages > epi ? stages : epi;
     static_assert(lds <= 160 * 1024, "halo tile does not fit the LDS");
+    const int tiles = (M / BM) * cdf_cdiv(a.Cout, BN);
+    if (plan) return cdf_plan_set(plan, CDF_FORM_HALO, BM, BN, NB, 1, W, tiles, tiles);
 #ifndef CDF_EMU
     static CdfDeviceLatch attr_done;
     if (attr_done.first()) {
         (void)hipFuncSetAttribute((const void*)conv_igemm_halo_kernel<W, BN, NB, BM, NS>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     }
 #endif
-    const int tiles = (M / BM) * cdf_cdiv(a.Cout, BN);
     CDF_LAUNCH((conv_igemm_halo_kernel<W, BN, NB, BM, NS>), dim3(tiles), dim3(512), lds, s, a);
     return cdf_check_launch("conv_igemm_halo");
 }
 
 
 template <int NS>
-static int launch_halo_ns(int W, bool n64, int bm, const SpxArgs& a, int M, hipStream_t s) {
+static int launch_halo_ns(int W, bool n64, int bm, const SpxArgs& a, int M, hipStream_t s, CdfPlan* plan) {
 #define CDF_HALO_CASE(WW)                                                                                              \
     if (W == WW) {                                                                                                     \
         if (bm == 256)                                                                                                 \
-            return n64 ? launch_igemm_halo<NS, WW, 64, 256>(a, M, s)                                                    \
-                       : launch_igemm_halo<NS, WW, 128, WW <= 64 ? 256 : 128>(a, M, s);                                 \
-        return n64 ? launch_igemm_halo<NS, WW, 64, 128>(a, M, s) : launch_igemm_halo<NS, WW, 128, 128>(a, M, s);        \
+            return n64 ? launch_igemm_halo<NS, WW, 64, 256>(a, M, s, plan)                                              \
+                       : launch_igemm_halo<NS, WW, 128, WW <= 64 ? 256 : 128>(a, M, s, plan);                           \
+        return n64 ? launch_igemm_halo<NS, WW, 64, 128>(a, M, s, plan) : launch_igemm_halo<NS, WW, 128, 128>(a, M, s, plan); \
     }
     CDF_HALO_CASE(128) CDF_HALO_CASE(64) CDF_HALO_CASE(32) CDF_HALO_CASE(16)
 #undef CDF_HALO_CASE
@@ -258,6 +259,6 @@ static int launch_halo_ns(int W, bool n64, int bm, const SpxArgs& a, int M, hipS
     return CDF_E_UNSUPPORTED;
 }
 
-int cdf_launch_igemm_halo(int ns, int W, bool n64, int bm, const SpxArgs& a, int M, hipStream_t s) {
-    return ns == 3 ? launch_halo_ns<3>(W, n64, bm, a, M, s) : launch_halo_ns<1>(W, n64, bm, a, M, s);
+int cdf_launch_igemm_halo(int ns, int W, bool n64, int bm, const SpxArgs& a, int M, hipStream_t s, CdfPlan* plan) {
+    return ns == 3 ? launch_halo_ns<3>(W, n64, bm, a, M, s, plan) : launch_halo_ns<1>(W, n64, bm, a, M, s, plan);
 }

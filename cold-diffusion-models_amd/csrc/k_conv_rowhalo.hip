@@ -287,14 +287,14 @@ __global__ void __launch_bounds__(512, 1) conv_igemm_rowhalo_stream_kernel(SpxAr
 }
 
 template <int NS, int W, int BN>
-static int launch_igemm_rowhalo_stream(const SpxArgs& a, int M, hipStream_t s, int reserve) {
+static int launch_igemm_rowhalo_stream(const SpxArgs& a, int M, hipStream_t s, int reserve, CdfPlan* plan) {
     constexpr int TH = 256 / W, RH = TH * (W + 2), HRP = (RH + 15) / 16 * 16;
     constexpr size_t st_a = (size_t)2 * HRP * 64, st_b = (size_t)2 * BN * 64;
     constexpr size_t lds_s = (st_a + 2 * st_b) + ((st_a + st_b) > (size_t)128 * (BN + 8) * 4 ? (st_a + st_b) : (size_t)128 * (BN + 8) * 4);
     static_assert(lds_s <= 160 * 1024, "streaming row-halo tile does not fit the LDS");
 #ifndef CDF_EMU
     static CdfDeviceLatch attr_done;
-    if (attr_done.first()) {
+    if (!plan && attr_done.first()) {
         (void)hipFuncSetAttribute((const void*)conv_igemm_rowhalo_stream_kernel<W, BN, NS, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         (void)hipFuncSetAttribute((const void*)conv_igemm_rowhalo_stream_kernel<W, BN, NS, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     }
@@ -311,6 +311,7 @@ static int launch_igemm_rowhalo_stream(const SpxArgs& a, int M, hipStream_t s, i
     if (ncu < 8) ncu = 8;
 #endif
     const int grid = tiles < ncu ? tiles : ncu;
+    if (plan) return cdf_plan_set(plan, CDF_FORM_ROWHALO, 256, BN, a.Cin == 64 ? 2 : 4, 1, W, tiles, grid);   // ("stages": channel chunks per tap row)
     if (a.Cin == 64)
         CDF_LAUNCH((conv_igemm_rowhalo_stream_kernel<W, BN, NS, 2>), dim3(grid), dim3(512), lds_s, s, a);
     else
@@ -322,9 +323,9 @@ static int launch_igemm_rowhalo_stream(const SpxArgs& a, int M, hipStream_t s, i
 // Widths with an instance: 128 (the default dispatch: the > 64-channel outputs at 128-pixel width) in the device build; the host SIMT-simulator
 // build also carries 64 / 32 / 16 (cdf_gemm_tuning.halo bit 64: the CPU suite drives the resident kernel at widths the simulator finishes in seconds).
 template <int NS>
-static int launch_rowhalo_ns(int W, bool n64, const SpxArgs& a, int M, hipStream_t s, int reserve) {
+static int launch_rowhalo_ns(int W, bool n64, const SpxArgs& a, int M, hipStream_t s, int reserve, CdfPlan* plan) {
 #define CDF_ROWHALO_CASE(WW) \
-    if (W == WW) return n64 ? launch_igemm_rowhalo_stream<NS, WW, 64>(a, M, s, reserve) : launch_igemm_rowhalo_stream<NS, WW, 128>(a, M, s, reserve);
+    if (W == WW) return n64 ? launch_igemm_rowhalo_stream<NS, WW, 64>(a, M, s, reserve, plan) : launch_igemm_rowhalo_stream<NS, WW, 128>(a, M, s, reserve, plan);
     CDF_ROWHALO_CASE(128)
 #ifdef CDF_EMU
     CDF_ROWHALO_CASE(64) CDF_ROWHALO_CASE(32) CDF_ROWHALO_CASE(16)
@@ -333,6 +334,6 @@ static int launch_rowhalo_ns(int W, bool n64, const SpxArgs& a, int M, hipStream
     return CDF_E_UNSUPPORTED;
 }
 
-int cdf_launch_igemm_rowhalo(int ns, int W, bool n64, const SpxArgs& a, int M, hipStream_t s, int reserve) {
-    return ns == 3 ? launch_rowhalo_ns<3>(W, n64, a, M, s, reserve) : launch_rowhalo_ns<1>(W, n64, a, M, s, reserve);
+int cdf_launch_igemm_rowhalo(int ns, int W, bool n64, const SpxArgs& a, int M, hipStream_t s, int reserve, CdfPlan* plan) {
+    return ns == 3 ? launch_rowhalo_ns<3>(W, n64, a, M, s, reserve, plan) : launch_rowhalo_ns<1>(W, n64, a, M, s, reserve, plan);
 }

@@ -318,19 +318,20 @@ extern "C" int cdf_gemm_tuning_default(cdf_gemm_tuning* t) {
 }
 
 template <int NS, int BM, int BN, int WM, int WN, int NSTAGE, int OCC = 512 / (64 * WM * WN)>
-static int launch_igemm_spx(const SpxArgs& a, int M, hipStream_t s) {
+static int launch_igemm_spx(const SpxArgs& a, int M, hipStream_t s, CdfPlan* plan) {
     constexpr size_t stages = (size_t)NSTAGE * 2 * (BM + BN) * 32 * sizeof(unsigned short) + (CDF_MAX_TAPS + 1) * sizeof(int);
     constexpr size_t epi = (size_t)BM * (BN + 8) * sizeof(float);
     constexpr size_t lds = stages > epi ? stages : epi;      // 128 x 128 x 2 stages: 68 KB (epilogue tile), two blocks per CU;
                                                              // 256 x 128 x 3 stages: 144 KB, one block per CU
     static_assert(lds <= 160 * 1024, "tile does not fit the LDS");
+    const int tiles = cdf_cdiv(M, BM) * cdf_cdiv(a.Cout, BN);
+    if (plan) return cdf_plan_set(plan, CDF_FORM_SPX, BM, BN, NSTAGE, a.ksplit > 1 ? a.ksplit : 1, 0, tiles, (long long)tiles * a.nphase * (a.ksplit > 1 ? a.ksplit : 1));
 #ifndef CDF_EMU
     static CdfDeviceLatch attr_done;
     if (attr_done.first()) {
         (void)hipFuncSetAttribute((const void*)conv_igemm_spx_kernel<BM, BN, WM, WN, NSTAGE, OCC, NS>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     }
 #endif
-    const int tiles = cdf_cdiv(M, BM) * cdf_cdiv(a.Cout, BN);
     CDF_LAUNCH((conv_igemm_spx_kernel<BM, BN, WM, WN, NSTAGE, OCC, NS>), dim3(tiles, a.nphase, a.ksplit > 1 ? a.ksplit : 1), dim3(64 * WM * WN), lds, s, a);
     if (a.ksplit > 1) {
         const int ftiles = cdf_cdiv(M, 16) * cdf_cdiv(a.Cout, BN);
@@ -356,7 +357,7 @@ extern "C" int cdf_conv_gemm_bf16x_ksplit(int M, int Cout, int nphase, int ntaps
 
 template <int NS>
 static int dispatch_gemm_bf16x(SpxArgs& a, int B, int H, int W, int Cin, int Cout, int QH, int QW, int os, int is, int nphase, long long ks_ws_floats,
-                               const cdf_gemm_tuning& T, hipStream_t s, int* bm_out = nullptr) {
+                               const cdf_gemm_tuning& T, hipStream_t s, int* bm_out = nullptr, CdfPlan* plan = nullptr) {
     // Tile choice: 64-wide N for Cout <= 64 (no half-empty MFMA columns); 64-row M tiles when 128-row tiles would
     // leave most of the 256 CUs x 2 resident blocks idle (deep, small-image layers: M = 8192 at 16 x 16); the 8-wave
     // 256 x 128 tile (3 stages, one block per CU) when it still gives every CU at least ~2 tiles.
@@ -401,7 +402,7 @@ static int dispatch_gemm_bf16x(SpxArgs& a, int B, int H, int W, int Cin, int Cou
         if (dx_ok && M % 256 == 0 && (T.rowhalo_stream & 1) && (Cin == 64 || Cin == 128) &&
             ((T.halo & 64) || ((T.halo & 32) && W == 128 && !n64 && (long long)(M / 256) * cdf_cdiv(Cout, 128) >= 256))) {
             if ((W == 128 || W == 64 || W == 32 || W == 16) && H % (256 / W) == 0) {
-                const int rc = cdf_launch_igemm_rowhalo(NS, W, n64, a, M, s, T.resident_reserve);
+                const int rc = cdf_launch_igemm_rowhalo(NS, W, n64, a, M, s, T.resident_reserve, plan);
                 if (rc != CDF_E_UNSUPPORTED) return rc;      // (no instance for this width in this build: the halo / generic kernels below take it)
             }
         }
@@ -412,12 +413,12 @@ static int dispatch_gemm_bf16x(SpxArgs& a, int B, int H, int W, int Cin, int Cou
                 const bool bm256 = (W <= 64 || n64) && T.halo_bm != 128 && H % (256 / W) == 0 && M % 256 == 0 &&
                                    (T.halo_bm == 256 || (long long)(M / 256) * cdf_cdiv(Cout, n64 ? 64 : 128) >= 256);
                 if (bm_out) *bm_out = bm256 ? 256 : 128;
-                return cdf_launch_igemm_halo(NS, W, n64, bm256 ? 256 : 128, a, M, s);
+                return cdf_launch_igemm_halo(NS, W, n64, bm256 ? 256 : 128, a, M, s, plan);
             }
         }
     }
     if (bm_out) *bm_out = bm;                               // (the generic kernels below take the row tile chosen above)
-    if (m256) return launch_igemm_spx<NS, 256, 128, 4, 2, 3>(a, M, s);
+    if (m256) return launch_igemm_spx<NS, 256, 128, 4, 2, 3>(a, M, s, plan);
     // Grids that do not even give every CU one 64-row tile (the 4 x 4 / 8 x 8-pixel levels of the 32 x 32 configurations, small
     // sampling batches): a block's life is its K loop, and with two stages every step waited out a whole DMA round trip (144 steps
     // of 1.5 us for 512 -> 1024 channels at 4 x 4 pixels).  Six stages, one block per CU: five chunks in flight per block.
@@ -433,12 +434,12 @@ static int dispatch_gemm_bf16x(SpxArgs& a, int B, int H, int W, int Cin, int Cou
         } else {
             a.ksplit = 1;
         }
-        if (n64) return launch_igemm_spx<NS, 64, 64, 2, 2, 6, 1>(a, M, s);
-        return launch_igemm_spx<NS, 64, 128, 2, 2, 6, 1>(a, M, s);
+        if (n64) return launch_igemm_spx<NS, 64, 64, 2, 2, 6, 1>(a, M, s, plan);
+        return launch_igemm_spx<NS, 64, 128, 2, 2, 6, 1>(a, M, s, plan);
     }
-    if (n64) return m64 ? launch_igemm_spx<NS, 64, 64, 2, 2, 2>(a, M, s) : launch_igemm_spx<NS, 128, 64, 2, 2, 2>(a, M, s);
-    if (m64) return launch_igemm_spx<NS, 64, 128, 2, 2, 2>(a, M, s);
-    return launch_igemm_spx<NS, 128, 128, 2, 2, 2>(a, M, s);
+    if (n64) return m64 ? launch_igemm_spx<NS, 64, 64, 2, 2, 2>(a, M, s, plan) : launch_igemm_spx<NS, 128, 64, 2, 2, 2>(a, M, s, plan);
+    if (m64) return launch_igemm_spx<NS, 64, 128, 2, 2, 2>(a, M, s, plan);
+    return launch_igemm_spx<NS, 128, 128, 2, 2, 2>(a, M, s, plan);
 }
 
 extern "C" int cdf_conv_gemm_bf16x_io(const void* x_hi, const void* x_lo, int ldx, const void* zero, const void* w_hi, const void* w_lo,
@@ -512,6 +513,36 @@ extern "C" int cdf_conv_gemm_bf16x_lnbwd_ok(int B, int H, int W, int Cin, int Co
     const long long M = (long long)B * H * W;
     return (Cout == 64 || Cout == 128) && nphase == 1 && ntaps == 9 && M % 256 == 0 && M < (1ll << 31) && Cin % 32 == 0 && Cin >= 64;
 }
+// the tuning cdf_conv_gemm_bf16x_lnbwd dispatches with: every kernel but the resident two-pass one runs the whole-tile epilogue this form
+// lives in; N tiles as wide as the layer
+static cdf_gemm_tuning lnbwd_tuning(const cdf_gemm_tuning* tune) {
+    cdf_gemm_tuning T = *cdf_tune(tune);
+    T.rowhalo_stream = 0; T.small_n64 = 0; T.tile_bn = 0; T.splitk = 0;
+    return T;
+}
+
+// The kernel a cdf_conv_gemm_bf16x[_io] call of this geometry launches (lnbwd = 1: a cdf_conv_gemm_bf16x_lnbwd call, which takes
+// H, W, Cin, Cout and the 3 x 3 phase descriptor only): dispatch_gemm_bf16x itself, stopped before the launch.
+extern "C" int cdf_conv_gemm_bf16x_form(int B, int H, int W, int Cin, int Cout, int QH, int QW, int os, int is, int nphase, const int* phase_desc,
+                                        int ns, long long ws_floats, int lnbwd, const cdf_gemm_tuning* tune, int* tiles_grid) {
+    CDF_REQUIRE(phase_desc && nphase >= 1 && nphase <= 4 && (ns == 1 || ns == 3) && B >= 1, "cdf_conv_gemm_bf16x_form: bad arguments");
+    CDF_TUNE_CHECK(tune, "cdf_conv_gemm_bf16x_form");
+    CDF_REQUIRE(!lnbwd || cdf_conv_gemm_bf16x_lnbwd_ok(B, H, W, Cin, Cout, nphase, phase_desc[2]), "cdf_conv_gemm_bf16x_form: not a geometry of cdf_conv_gemm_bf16x_lnbwd");
+    SpxArgs a = {};
+    a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.QH = QH; a.QW = QW; a.os = os; a.is = is; a.nphase = nphase;
+    int rc = fill_phases(a.ph, nphase, phase_desc, "cdf_conv_gemm_bf16x_form");
+    if (rc) return rc;
+    static float ws_token;                                   // (the dispatcher only asks whether a workspace was given; nothing is launched)
+    a.ksplit = 1; a.ks_ws = (ws_floats > 0 && !lnbwd) ? &ws_token : nullptr; a.ks_ld = 0;
+    const cdf_gemm_tuning T = lnbwd ? lnbwd_tuning(tune) : *cdf_tune(tune);
+    CdfPlan plan = {0, 0, 0};
+    rc = ns == 3 ? dispatch_gemm_bf16x<3>(a, B, H, W, Cin, Cout, QH, QW, os, is, nphase, a.ks_ws ? ws_floats : 0, T, nullptr, nullptr, &plan)
+                 : dispatch_gemm_bf16x<1>(a, B, H, W, Cin, Cout, QH, QW, os, is, nphase, a.ks_ws ? ws_floats : 0, T, nullptr, nullptr, &plan);
+    if (rc) return rc;
+    if (tiles_grid) { tiles_grid[0] = plan.tiles; tiles_grid[1] = plan.grid; }
+    return plan.code;
+}
+
 extern "C" int cdf_conv_gemm_bf16x_lnbwd(const void* x_hi, const void* x_lo, int ldx, const void* zero, const void* w_hi, const void* w_lo, int ldk,
                                          int B, int H, int W, int Cin, int Cout, const int* phase_desc, const float* ln_x, int ld_lnx,
                                          const float* ln_mean, const float* ln_rstd, const float* ln_g, float* dh, int lddh, float* dg, float* db,
@@ -536,9 +567,7 @@ extern "C" int cdf_conv_gemm_bf16x_lnbwd(const void* x_hi, const void* x_lo, int
     int rc = fill_phases(a.ph, 1, phase_desc, "cdf_conv_gemm_bf16x_lnbwd");
     if (rc) return rc;
     a.ksplit = 1; a.ks_ws = nullptr; a.ks_ld = 0;
-    // every kernel but the resident two-pass one runs the whole-tile epilogue this form lives in; N tiles as wide as the layer
-    cdf_gemm_tuning T = *cdf_tune(tune);
-    T.rowhalo_stream = 0; T.small_n64 = 0; T.tile_bn = 0; T.splitk = 0;
+    const cdf_gemm_tuning T = lnbwd_tuning(tune);
     int bm = 0;
     rc = x_lo ? dispatch_gemm_bf16x<3>(a, B, H, W, Cin, Cout, H, W, 1, 1, 1, 0, T, CDF_S, &bm) : dispatch_gemm_bf16x<1>(a, B, H, W, Cin, Cout, H, W, 1, 1, 1, 0, T, CDF_S, &bm);
     if (rc) return rc;

@@ -500,17 +500,18 @@ __global__ void __launch_bounds__(512, 1) conv_wgrad_row3_kernel(SpxWgradArgs a)
 }
 
 template <int NS, int TA, int TB, bool STACK2 = false>
-static int launch_wgrad_spx(const SpxWgradArgs& a, hipStream_t s) {
+static int launch_wgrad_spx(const SpxWgradArgs& a, hipStream_t s, CdfPlan* plan) {
     constexpr size_t stage = (size_t)2 * 32 * ((TA + 32) + (TB + 32)) * sizeof(unsigned short);
     constexpr size_t epi = (size_t)TA * (TB + 8) * sizeof(float);
     constexpr size_t lds = 2 * stage > epi ? 2 * stage : epi;
+    const int tiles = (STACK2 ? 1 : cdf_cdiv(a.CA, TA)) * cdf_cdiv(a.CB, TB);
+    if (plan) return cdf_plan_set(plan, STACK2 ? CDF_FORM_WGRAD_STACK2 : CDF_FORM_WGRAD_SPX, TA, TB, 0, 0, 0, tiles, (long long)tiles * (STACK2 ? cdf_cdiv(a.ntaps, 2) : a.ntaps) * a.nsplit);
 #ifndef CDF_EMU
     static CdfDeviceLatch attr_done;
     if (attr_done.first()) {
         (void)hipFuncSetAttribute((const void*)conv_wgrad_spx_kernel<TA, TB, STACK2, NS>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     }
 #endif
-    const int tiles = (STACK2 ? 1 : cdf_cdiv(a.CA, TA)) * cdf_cdiv(a.CB, TB);
     CDF_LAUNCH((conv_wgrad_spx_kernel<TA, TB, STACK2, NS>), dim3(tiles, STACK2 ? cdf_cdiv(a.ntaps, 2) : a.ntaps, a.nsplit), dim3(256), lds, s, a);
     return cdf_check_launch("conv_wgrad_spx");
 }
@@ -523,24 +524,25 @@ extern "C" int cdf_conv_wgrad_bf16x_is_row3(int QH, int QW, int CA, int CB, int 
 }
 
 template <int NS, int TA, int TB>
-static int launch_wgrad_row3(const SpxWgradArgs& a, hipStream_t s) {
+static int launch_wgrad_row3(const SpxWgradArgs& a, hipStream_t s, CdfPlan* plan) {
     constexpr size_t stage = (size_t)2 * (36 * (TA + 32) + 32 * (TB + 32)) * sizeof(unsigned short);
     constexpr size_t epi = (size_t)TA * (TB + 8) * sizeof(float);
     constexpr size_t lds = 2 * stage > epi ? 2 * stage : epi;
+    const int tiles = cdf_cdiv(a.CA, TA) * cdf_cdiv(a.CB, TB);
+    if (plan) return cdf_plan_set(plan, CDF_FORM_WGRAD_ROW3, TA, TB, 0, 0, 0, tiles, (long long)tiles * 3 * a.nsplit);
 #ifndef CDF_EMU
     static CdfDeviceLatch attr_done;
     if (attr_done.first()) {
         (void)hipFuncSetAttribute((const void*)conv_wgrad_row3_kernel<TA, TB, NS>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     }
 #endif
-    const int tiles = cdf_cdiv(a.CA, TA) * cdf_cdiv(a.CB, TB);
     CDF_LAUNCH((conv_wgrad_row3_kernel<TA, TB, NS>), dim3(tiles, 3, a.nsplit), dim3(512), lds, s, a);
     return cdf_check_launch("conv_wgrad_row3");
 }
 
 template <int NS>
 static int dispatch_wgrad_bf16x(SpxWgradArgs& a, int QH, int QW, int HA, int WA, int sa, int HB, int WB, int sb, int CA, int CB, int ntaps,
-                                const cdf_gemm_tuning& T, hipStream_t s) {
+                                const cdf_gemm_tuning& T, hipStream_t s, CdfPlan* plan = nullptr) {
     // 3 x 3 stride-1 "same" convolutions (X shifted per tap, dY read in place): one block per row of taps
     if (T.wgrad_row3 && ntaps == 9 && sa == 1 && sb == 1 && HA == QH && WA == QW && HB == QH && WB == QW &&
         (QW == 16 || QW == 32 || QW == 64 || QW == 128) && (QH * QW) % 32 == 0 && (QW >= 32 || QH % (32 / QW) == 0) && !(CA <= 64 && CB <= 64)) {
@@ -555,21 +557,47 @@ static int dispatch_wgrad_bf16x(SpxWgradArgs& a, int QH, int QW, int HA, int WA,
             ok = ok && seen == 7;
         }
         if (ok) {
-            if (CA <= 64) return launch_wgrad_row3<NS, 64, 128>(a, s);
-            if (CB <= 64) return launch_wgrad_row3<NS, 128, 64>(a, s);
-            return launch_wgrad_row3<NS, 128, 128>(a, s);
+            if (CA <= 64) return launch_wgrad_row3<NS, 64, 128>(a, s, plan);
+            if (CB <= 64) return launch_wgrad_row3<NS, 128, 64>(a, s, plan);
+            return launch_wgrad_row3<NS, 128, 128>(a, s, plan);
         }
     }
     // thin layers get 64-wide tiles so that no half of a tile multiplies padding
-    if (CA <= 64 && CB <= 64) return launch_wgrad_spx<NS, 64, 64>(a, s);
+    if (CA <= 64 && CB <= 64) return launch_wgrad_spx<NS, 64, 64>(a, s, plan);
     if (CA <= 64) {
         bool same_b = ntaps >= 2;                  // two taps can share the B rows only if B is read at one offset
         for (int t = 1; t < ntaps; ++t) same_b = same_b && a.dby[t] == a.dby[0] && a.dbx[t] == a.dbx[0];
-        if (same_b && T.wgrad_stack) return launch_wgrad_spx<NS, 128, 128, true>(a, s);
-        return launch_wgrad_spx<NS, 64, 128>(a, s);
+        if (same_b && T.wgrad_stack) return launch_wgrad_spx<NS, 128, 128, true>(a, s, plan);
+        return launch_wgrad_spx<NS, 64, 128>(a, s, plan);
     }
-    if (CB <= 64) return launch_wgrad_spx<NS, 128, 64>(a, s);
-    return launch_wgrad_spx<NS, 128, 128>(a, s);
+    if (CB <= 64) return launch_wgrad_spx<NS, 128, 64>(a, s, plan);
+    return launch_wgrad_spx<NS, 128, 128>(a, s, plan);
+}
+
+static void fill_wgrad_taps(SpxWgradArgs& a, int ntaps, const int* tap_desc) {
+    for (int t = 0; t < ntaps; ++t) {
+        a.day[t] = (signed char)tap_desc[4 * t + 0];
+        a.dax[t] = (signed char)tap_desc[4 * t + 1];
+        a.dby[t] = (signed char)tap_desc[4 * t + 2];
+        a.dbx[t] = (signed char)tap_desc[4 * t + 3];
+    }
+}
+
+// The kernel a cdf_conv_wgrad_bf16x call of this geometry launches: dispatch_wgrad_bf16x itself, stopped before the launch.
+extern "C" int cdf_conv_wgrad_bf16x_form(int QH, int QW, int HA, int WA, int sa, int HB, int WB, int sb, int CA, int CB, int ntaps, const int* tap_desc,
+                                         int ns, int nsplit, const cdf_gemm_tuning* tune, int* tiles_grid) {
+    CDF_REQUIRE(ntaps >= 1 && ntaps <= CDF_MAX_TAPS && tap_desc && nsplit >= 1 && (ns == 1 || ns == 3), "cdf_conv_wgrad_bf16x_form: bad arguments");
+    CDF_TUNE_CHECK(tune, "cdf_conv_wgrad_bf16x_form");
+    SpxWgradArgs a = {};
+    a.QH = QH; a.QW = QW; a.HA = HA; a.WA = WA; a.sa = sa; a.HB = HB; a.WB = WB; a.sb = sb;
+    a.CA = CA; a.CB = CB; a.ntaps = ntaps; a.nsplit = nsplit;
+    fill_wgrad_taps(a, ntaps, tap_desc);
+    CdfPlan plan = {0, 0, 0};
+    const int rc = ns == 3 ? dispatch_wgrad_bf16x<3>(a, QH, QW, HA, WA, sa, HB, WB, sb, CA, CB, ntaps, *cdf_tune(tune), nullptr, &plan)
+                           : dispatch_wgrad_bf16x<1>(a, QH, QW, HA, WA, sa, HB, WB, sb, CA, CB, ntaps, *cdf_tune(tune), nullptr, &plan);
+    if (rc) return rc;
+    if (tiles_grid) { tiles_grid[0] = plan.tiles; tiles_grid[1] = plan.grid; }
+    return plan.code;
 }
 
 extern "C" int cdf_conv_wgrad_bf16x(const void* a_hi, const void* a_lo, int lda, const void* b_hi, const void* b_lo, int ldb,
@@ -590,12 +618,7 @@ extern "C" int cdf_conv_wgrad_bf16x(const void* a_hi, const void* a_lo, int lda,
     a.CA = CA; a.CB = CB; a.ntaps = ntaps; a.nsplit = nsplit; a.xcd_swizzle = cdf_tune(tune)->wgrad_swizzle;
     const int M = B * QH * QW;
     a.m_per_split = cdf_cdiv(cdf_cdiv(M, nsplit), 32) * 32;
-    for (int t = 0; t < ntaps; ++t) {
-        a.day[t] = (signed char)tap_desc[4 * t + 0];
-        a.dax[t] = (signed char)tap_desc[4 * t + 1];
-        a.dby[t] = (signed char)tap_desc[4 * t + 2];
-        a.dbx[t] = (signed char)tap_desc[4 * t + 3];
-    }
+    fill_wgrad_taps(a, ntaps, tap_desc);
     return a_lo ? dispatch_wgrad_bf16x<3>(a, QH, QW, HA, WA, sa, HB, WB, sb, CA, CB, ntaps, *cdf_tune(tune), CDF_S)
                 : dispatch_wgrad_bf16x<1>(a, QH, QW, HA, WA, sa, HB, WB, sb, CA, CB, ntaps, *cdf_tune(tune), CDF_S);
 }

@@ -251,6 +251,22 @@ int cdf_conv_gemm_io(const float* x, int ldx, const float* w, int ldw, float* y,
                      const void* mul, int ldm, int act, int mul_mode, int accumulate, int b_trans, int batch,
                      long long x_bs, long long w_bs, long long y_bs, int batch2, long long x_bs2, long long w_bs2,
                      long long y_bs2, int io_bf16, void* y_hi, int ld_ys, void* stream);
+/* Kernel-form queries (host side, nothing is launched): WHICH kernel a cdf_conv_gemm_bf16x[_io] / cdf_conv_wgrad_bf16x call of this geometry
+ * takes.  They run the library's own dispatch code up to the launch, so they cannot drift from it; tests use them to prove that every
+ * kernel form the product reaches has a test at that shape.  Return value > 0:
+ *   form << 24 | (BM / 64) << 20 | (BN / 64) << 16 | stages << 12 | ksplit << 4 | (W / 16)
+ *   GEMM form 1: resident row-halo stream kernel (BM 256; `stages` = 32-channel chunks per tap row: 2 or 4; W = its image-width instance),
+ *             2: LDS-resident-input (halo) kernel (stages = weight stages; W = its image-width instance),
+ *             3: generic gather-GEMM (stages 2, 3 or 6; ksplit > 1: split-K through the workspace + finish kernel; W field 0).
+ *   weight-gradient form 1: one block per row of taps, 2: one block per tap, 3: two stacked taps per 128-row tile; BM / BN = the CA / CB
+ *             tile, the other fields 0.
+ * ns = 3 (hi + lo planes) or 1 (hi only); ws_floats = the split-K workspace the call would pass (0: none); lnbwd = 1: the form of a
+ * cdf_conv_gemm_bf16x_lnbwd call (QH = H, QW = W, os = is = nphase = 1).  tiles_grid (nullable) receives {output tiles, blocks launched}:
+ * blocks < tiles means resident blocks that walk several tiles each.  Negative: CDF_E_*. */
+int cdf_conv_gemm_bf16x_form(int B, int H, int W, int Cin, int Cout, int QH, int QW, int os, int is, int nphase, const int* phase_desc,
+                             int ns, long long ws_floats, int lnbwd, const cdf_gemm_tuning* tune, int* tiles_grid);
+int cdf_conv_wgrad_bf16x_form(int QH, int QW, int HA, int WA, int sa, int HB, int WB, int sb, int CA, int CB, int ntaps,
+                              const int* tap_desc, int ns, int nsplit, const cdf_gemm_tuning* tune, int* tiles_grid);
 /* cdf_conv_wgrad_bf16x_is_row3 tells the caller whether a geometry takes the row-of-taps kernel (3 tap blocks per tile, one 512-thread
  * block per CU) so that it can size nsplit. */
 int cdf_conv_wgrad_bf16x_is_row3(int QH, int QW, int CA, int CB, int ntaps, int same_size_3x3, const cdf_gemm_tuning* tune);

@@ -124,10 +124,9 @@ def test_sampler_twice_and_poisoned_bit_identical(bench_data):
     _same(first, poisoned, "poisoned run")
 
 
-def test_config2_model_twice_and_poisoned_bit_identical():
-    """BASELINE config 2: Model(ch=128, (1, 2, 2, 2), 2 res blocks, attention at 16 x 16, dropout 0.1) at 32 x 32, B = 128, forward +
-    backward: output, input gradient and every parameter gradient, twice and once on poisoned allocations (the dropout seed is drawn
-    from torch's generator, reseeded per run)."""
+def _config2_runner():
+    """BASELINE config 2: Model(ch=128, (1, 2, 2, 2), 2 res blocks, attention at 16 x 16, dropout 0.1) at 32 x 32, B = 128: a function that
+    runs forward + backward from the same state and returns output, input gradient and every parameter gradient."""
     from deblurring_diffusion_pytorch import Model
     from colddiff import runtime as rt
     kw = dict(resolution=32, in_channels=3, out_ch=3, ch=128, ch_mult=(1, 2, 2, 2), num_res_blocks=2, attn_resolutions=(16,), dropout=0.1)
@@ -146,6 +145,13 @@ def test_config2_model_twice_and_poisoned_bit_identical():
         y.backward(gy.to(DEV))
         torch.cuda.synchronize()
         return [y.detach().cpu(), xd.grad.cpu()] + [p.grad.cpu().clone() for p in net.parameters()]
+    return run
+
+
+def test_config2_model_twice_and_poisoned_bit_identical():
+    """BASELINE config 2 (see _config2_runner), forward + backward: twice and once on poisoned allocations (the dropout seed is drawn from
+    torch's generator, reseeded per run)."""
+    run = _config2_runner()
     first = run()
     second = run()
     with poisoned_allocations():
@@ -158,16 +164,18 @@ def test_config2_model_twice_and_poisoned_bit_identical():
 # coverage guard: every entry point on the hot path names the test(s) that run it at a production shape
 # ------------------------------------------------------------------------------------------------------------------------------------
 _KP = "test_kernels_production.py::"
+_GP = "test_gemm_production.py::"
 _K = "test_kernels.py::"
 _P2 = "test_gpu_parity2.py::"
 _BS = "test_gpu_invariance.py::test_bench_step_twice_poisoned_and_reserved_bit_identical"
 COVERED_AT_PRODUCTION_SHAPE = {
     # GEMM family: the *_large GPU tests run the shapes the bench / configs launch; the step-level tests above run them in the step
     "cdf_conv_gemm": [_K + "test_conv_gemm_large", _K + "test_conv_presplit_large"],
-    "cdf_conv_gemm_bf16x": [_K + "test_conv_presplit_large", _K + "test_specialised_epilogue_equals_generic_large"],
-    "cdf_conv_gemm_bf16x_lnbwd": [_K + "test_conv_dgrad_with_layernorm_backward_epilogue_large"],
-    "cdf_conv_wgrad": [_K + "test_conv_gemm_large"],
-    "cdf_conv_wgrad_bf16x": [_K + "test_conv_presplit_large"],
+    # ... and the pre-split family, form by form (test_coverage_guard below), in test_gemm_production.py
+    "cdf_conv_gemm_bf16x": [_GP + "test_gemm_bench_forms", _K + "test_conv_presplit_large", _K + "test_specialised_epilogue_equals_generic_large"],
+    "cdf_conv_gemm_bf16x_lnbwd": [_GP + "test_gemm_bench_forms", _K + "test_conv_dgrad_with_layernorm_backward_epilogue_large"],
+    "cdf_conv_wgrad": [_GP + "test_wgrad_f32_995_slabs_two_empty", _K + "test_conv_gemm_large"],
+    "cdf_conv_wgrad_bf16x": [_GP + "test_wgrad_bench_forms_and_split_counts", _K + "test_conv_presplit_large"],
     "cdf_split_bf16": [_K + "test_conv_presplit_large"],
     "cdf_bf16x_ksplit": [_K + "test_conv_presplit_large"],
     "cdf_wgrad_nsplit": [_KP + "test_unpack_reduce_bench_slab_counts"],
@@ -217,7 +225,7 @@ COVERED_AT_PRODUCTION_SHAPE = {
     # (same tile walk and split; the flag changes only how operands are loaded and stored), so the *_large tests run their production
     # shapes; the bf16 step at the bench shape runs the bf16 operands
     "cdf_conv_gemm_io": [_K + "test_conv_gemm_large", _P2 + "test_bf16_mode_bench_shape_fused_step"],
-    "cdf_conv_gemm_bf16x_io": [_K + "test_conv_presplit_large", _P2 + "test_bf16_mode_bench_shape_fused_step"],
+    "cdf_conv_gemm_bf16x_io": [_GP + "test_gemm_bench_forms", _K + "test_conv_presplit_large", _P2 + "test_bf16_mode_bench_shape_fused_step"],
     # elementwise bf16 -> fp32 widening (exactness: test_bf16_storage.py::test_bf16_to_f32_and_back)
     "cdf_bf16_to_f32": [_P2 + "test_bf16_mode_bench_shape_fused_step", "test_bf16_storage.py::test_bf16_to_f32_and_back"],
     # GEMM-class entry points in the plain bf16 arithmetic
@@ -239,34 +247,79 @@ EXEMPT = {
     "cdf_conv_gemm_bf16x_ksplit": "host-side query (split count)",
     "cdf_conv_gemm_bf16x_lnbwd_ok": "host-side query (epilogue eligibility)",
     "cdf_conv_wgrad_bf16x_is_row3": "host-side query (kernel form)",
+    "cdf_conv_gemm_bf16x_form": "host-side query (kernel form: the dispatcher, stopped before the launch)",
+    "cdf_conv_wgrad_bf16x_form": "host-side query (kernel form: the dispatcher, stopped before the launch)",
 }
+
+
+_GEMM_FAMILY = ("cdf_conv_gemm_bf16x", "cdf_conv_gemm_bf16x_io", "cdf_conv_gemm_bf16x_lnbwd", "cdf_conv_wgrad_bf16x", "cdf_conv_wgrad")
 
 
 def _guard_calls(bench_data):
     """Every cdf_* call of one bench step in each arithmetic mode the bench reports (bf16x3, and bf16 with its bf16 activation
-    stream) and of one sampler step: (set of names, the (nsplit, T, R, C) of the bf16x3 step's slab reductions)."""
+    stream) and of one sampler step: (set of names, the (nsplit, T, R, C) of the bf16x3 step's slab reductions, the (recording, name,
+    arguments) of every pre-split GEMM / weight-gradient call of those and of one forward + backward pass of config 2's network -- the
+    phase / tap descriptors copied, they are buffers the caller may reuse)."""
     from colddiff import runtime as rt
-    names, unpack = set(), set()
+    names, unpack, gemm = set(), set(), []
+
+    def keep(src, rec):
+        for n, a in rec.calls:
+            if n in _GEMM_FAMILY:
+                gemm.append((src, n, tuple(tuple(v) if hasattr(v, "_length_") else v for v in a)))
     for mode in ("bf16x3", "bf16"):
         with rt.precision_scope(mode), Recorder(rt.lib()) as rec:
             _step(bench_data)
         names |= rec.names()
+        keep("bench " + mode, rec)
         if mode == "bf16x3":
             unpack = {tuple(a[2:6]) for n, a in rec.calls if n in ("cdf_unpack_reduce", "cdf_unpack_reduce_bias")}
     torch.manual_seed(4)
     with Recorder(rt.lib()) as rec:
         _sampler_run(bench_data["sd"], torch.randn(16, 3, 128, 128))
-    return names | rec.names(), unpack
+    keep("sampler", rec)
+    run2 = _config2_runner()
+    with Recorder(rt.lib()) as rec2:
+        run2()
+    keep("config 2", rec2)
+    return names | rec.names(), unpack, gemm
+
+
+def _c_ints(v):
+    import ctypes
+    return (ctypes.c_int * len(v))(*v)
+
+
+def _gemm_code(L, name, a):
+    """The kernel-form code of a recorded cdf_conv_gemm_bf16x / _io / _lnbwd call: the query on the recorded arguments themselves."""
+    ns = 3 if a[1] else 1
+    if name.endswith("_lnbwd"):
+        B, H, W, Cin, Cout = a[7:12]
+        return L.cdf_conv_gemm_bf16x_form(B, H, W, Cin, Cout, H, W, 1, 1, 1, _c_ints(a[12]), ns, 0, 1, a[-2], 0)
+    B, H, W, Cin, OH, OW, Cout, QH, QW, os_, is_, nphase = a[9:21]
+    ws, ws_floats = a[-4], a[-3]
+    return L.cdf_conv_gemm_bf16x_form(B, H, W, Cin, Cout, QH, QW, os_, is_, nphase, _c_ints(a[21]), ns, ws_floats if ws else 0, 0, a[-2], 0)
+
+
+def _wgrad_code(L, name, a):
+    QH, QW, HA, WA, sa, HB, WB, sb, CA, CB, ntaps = a[10:21]
+    return L.cdf_conv_wgrad_bf16x_form(QH, QW, HA, WA, sa, HB, WB, sb, CA, CB, ntaps, _c_ints(a[21]), 3 if a[1] else 1, a[22], a[-2], 0)
 
 
 def test_coverage_guard(bench_data):
     """A new entry point cannot reach the hot path without a test at a production shape: each name one bench step (both modes) and one
     sampler step call must be listed above (or exempt, with a reason), and each listed test must exist.  The slab counts
-    test_kernels_production.BENCH_UNPACK tests must still be ones the bench step launches (stale shapes fail here)."""
+    test_kernels_production.BENCH_UNPACK tests must still be ones the bench step launches (stale shapes fail here).
+    The pre-split GEMM family is guarded kernel form by kernel form, not by entry-point name: every (form code, NS) that the bench step,
+    the sampler step and config 2's network reach -- asked of the library's own dispatcher (cdf_conv_gemm_bf16x_form /
+    cdf_conv_wgrad_bf16x_form) with the recorded arguments -- must be a form some test_gemm_production.BENCH_GEMM / BENCH_WGRAD row resolves
+    to, and every committed row must still be a call the recordings contain."""
     import os
     import re
     from test_kernels_production import BENCH_UNPACK
-    names, unpack = _guard_calls(bench_data)
+    from colddiff import runtime as rt
+    import test_gemm_production as gp
+    names, unpack, gemm = _guard_calls(bench_data)
     here = os.path.dirname(os.path.abspath(__file__))
     for name, tests in COVERED_AT_PRODUCTION_SHAPE.items():
         for t in tests:
@@ -277,3 +330,26 @@ def test_coverage_guard(bench_data):
     assert not missing, "hot-path entry points without a production-shape test: %s" % missing
     stale = sorted(set(BENCH_UNPACK) - unpack)
     assert not stale, "BENCH_UNPACK shapes the bench step no longer launches: %s (it launches %s)" % (stale, sorted(unpack))
+    # ---- the pre-split GEMM family, form by form
+    L = rt.lib()
+    reached_g, reached_w, rows_g, rows_w = {}, {}, set(), set()
+    for src, name, a in gemm:
+        if name == "cdf_conv_wgrad_bf16x":
+            reached_w.setdefault((_wgrad_code(L, name, a), 3 if a[1] else 1), (src, a[9:21], a[22]))
+            rows_w.add(gp.wgrad_row(name, a))
+        elif name != "cdf_conv_wgrad":
+            reached_g.setdefault((_gemm_code(L, name, a), 3 if a[1] else 1), (src, name, a[9:21]))
+            rows_g.add(gp.gemm_row(name, a))
+    assert all(c > 0 for c, _ in list(reached_g) + list(reached_w)), (reached_g, reached_w)
+    tested_g = {(gp.gemm_form(L, r, rt.tune_ptr())[0], r[-1]) for r in gp.BENCH_GEMM}
+    tested_w = {(gp.wgrad_form(L, r, rt.tune_ptr())[0], r[-1]) for r in gp.BENCH_WGRAD}
+    for what, reached, tested, dec in (("GEMM", reached_g, tested_g, gp.decode), ("weight-gradient", reached_w, tested_w, gp.decode)):
+        print("pre-split %s kernel forms reached: %s" % (what, sorted((k[1], tuple(dec(k[0]).items())) for k in reached)))
+        untested = {k: v for k, v in reached.items() if k not in tested}
+        assert not untested, "%s kernel forms (code, NS) the product reaches without a test_gemm_production row: %s" % (
+            what, {(ns, tuple(dec(c).items())): v for (c, ns), v in untested.items()})
+    stale = sorted(set(gp.BENCH_GEMM) - rows_g) + sorted(set(gp.BENCH_WGRAD) - rows_w)
+    assert not stale, "test_gemm_production rows the recordings no longer contain: %s" % stale
+    resident = [(r, gp.gemm_form(L, r, rt.tune_ptr())[1:]) for r in gp.BENCH_GEMM if gp.decode(gp.gemm_form(L, r, rt.tune_ptr())[0])["form"] == gp.ROWHALO]
+    print("resident row-halo rows (tiles, grid):", resident)
+    assert any(t > g for _, (t, g) in resident), "no BENCH_GEMM row walks several tiles per resident block"
