@@ -20,7 +20,7 @@ import torch
 from . import functions as F_
 from . import ops
 from . import runtime as rt
-from .functions import _conv_plans, _done, _used
+from .functions import _done, _used
 
 ACT_GELU = F_.ACT_GELU
 
@@ -43,35 +43,14 @@ def block_ok(m):
 
 # -- dense convolutions on bf16 tensors ------------------------------------------------------------------------------------------------
 def conv_fwd(x, Cin, weight, bias, kind="conv", stride=1, pad=None, **epi):
-    k = weight.shape[-1]
-    if pad is None:
-        pad = (k // 2,) * 4
-    _, H, W, _ = x.shape
-    plan = _conv_plans(kind, H, W, k, stride, pad)[0]
-    Cout = weight.shape[0] if kind == "conv" else weight.shape[1]
+    plan, _, _, Cout, _ = F_.conv_geom(x, weight, kind, stride, pad)
     wp = ops.packed(weight, ("conv_fwd" if kind == "conv" else "convT_fwd") + "_sp")
     return ops.conv_gemm_bf(plan, x, Cin, wp, Cout, bias=bias, **epi)
 
 
 def conv_bwd(x, Cin, dy, weight, bias, kind="conv", stride=1, pad=None, need_dx=True, mul=None, mul_mode=0):
     """Weight / bias gradients accumulated (fp32), data gradient returned as a bf16 tensor (optionally x GELU'(mul))."""
-    k = weight.shape[-1]
-    if pad is None:
-        pad = (k // 2,) * 4
-    _, H, W, _ = x.shape
-    _, pd, pw = _conv_plans(kind, H, W, k, stride, pad)
-    KK = k * k
-    if kind == "conv":
-        Cout = weight.shape[0]
-        s_r, s_c = KK, Cin * KK
-    else:
-        Cout = weight.shape[1]
-        s_r, s_c = Cout * KK, KK
-    fuse_bias = bias is not None and kind == "conv"
-    ops.wgrad_into(ops.grad_of(weight), pw, x, Cin, dy, Cout, 1, s_r, s_c, gbias=ops.grad_of(bias) if fuse_bias else None,
-                   xa_s=(x, None), xb_s=(dy, None))
-    if bias is not None and not fuse_bias:
-        ops.colsum_into(ops.grad_of(bias), dy, Cout)
+    pd, Cout, _ = F_.conv_param_grads(x, Cin, dy, weight, bias, kind, stride, pad, (x, None), (dy, None))
     if not need_dx:
         return None
     wd = ops.packed(weight, ("conv_dgrad" if kind == "conv" else "convT_dgrad") + "_sp")
@@ -195,90 +174,15 @@ class ConvNextBlockBF(torch.autograd.Function):
 
 class LinAttnBlockBF(torch.autograd.Function):
     """Residual(PreNorm(LinearAttention)) on the bf16 stream.  The block's inside -- LayerNorm output, k | v, softmax statistics, context,
-    the per-image folded matrices -- is the fp32 computation of F_.LinAttnBlockFn (q folded form; its k | v GEMM takes bf16 operands
-    in this mode as before); the stream tensors x / y / dy / dx cross the block's boundary as bf16: LayerNorm reads bf16 x, the output
+    the per-image folded matrices -- is the fp32 computation of F_.LinAttnBlockFn, the same body (F_.linattn_block_forward / _backward; q
+    folded form: its k | v GEMM takes bf16 operands in this mode as before); the stream tensors x / y / dy / dx cross the block's boundary as bf16: LayerNorm reads bf16 x, the output
     product's residual operand is read as bf16, y is rounded once when stored, the LayerNorm backward adds the bf16 residual gradient and
     stores bf16."""
 
     @staticmethod
     def forward(ctx, anchor, x, m, dest=None):
-        y, saved = _attn_forward(ctx, x, m, dest)
-        ctx.save_for_backward(*saved)
-        return y
+        return F_.linattn_block_forward(ctx, x, m, dest, True)
 
     @staticmethod
     def backward(ctx, dy):
-        return _attn_backward(ctx, dy)
-
-
-def _attn_forward(ctx, x, m, dest):
-    norm, att = m.fn.norm, m.fn.fn
-    dim = x.shape[-1]
-    grad_on = ctx.needs_input_grad[0]
-    ctx.qfold = dim % 8 == 0 and dim <= att.heads * 32 and att.heads <= 4 and F_._ATTN_FUSED >= 1 and F_._ATTN_QFOLD
-    ctx.kv_planes = bool(grad_on and ctx.qfold and F_.kv_planes_ok(x, dim, att.heads))     # k | v backward on operand planes (functions.py)
-    if ctx.kv_planes:
-        xn, mean, rstd, xnb = ops.layernorm_fwd_bf(x, norm.g, norm.b, norm.eps, grad_on, out_f32=True, planes=True)
-    else:
-        (xn, mean, rstd), xnb = ops.layernorm_fwd_bf(x, norm.g, norm.b, norm.eps, grad_on, out_f32=True), None
-    ctx.m = m
-    _used(ctx, norm, att.to_qkv, att.to_out)
-    if ctx.qfold:
-        # (the 128- and 64-pixel levels of the CelebA net: 80 % of the attention bytes) the output product reads the residual from the bf16
-        # stream and writes its result into it (cdf_conv_gemm_io): x and y cross the boundary once each, as bf16
-        if F_._ATTN_KVCTX and ops.linattn_kvctx_ok(xn, dim, att.heads):
-            kv, cx, cxs, kmax, ksum = ops.linattn_kvctx(xn, dim, att.to_qkv.weight, att.heads, att.scale)
-        else:
-            kv = F_.kv_forward(xn, dim, att.to_qkv.weight)
-            cx, cxs, kmax, ksum = ops.linattn_context(kv, att.heads, att.scale, koff=0)
-        yb, Mb, Nb = ops.linattn_fold(xn, cxs, att.to_qkv.weight, att.to_out.weight, att.to_out.bias, x, att.heads,
-                                      y=dest.second() if dest is not None else None)
-        return yb, (x, xn, mean, rstd, kv, Mb, cx, cxs, kmax, ksum, Nb, xnb)
-    xf = ops.to_f32(x)                                          # (deeper levels: the plain forms keep an fp32 residual operand)
-    qkv = F_.conv_forward(xn, dim, att.to_qkv.weight, None)
-    ctx.fused = dim % 4 == 0 and (F_._ATTN_FUSED == 2 or (F_._ATTN_FUSED == 1 and dim <= att.heads * 32))
-    if ctx.fused:
-        cx, cxs, kmax, ksum = ops.linattn_context(qkv, att.heads, att.scale)
-        y, Mb = ops.linattn_project(qkv, cxs, att.to_out.weight, att.to_out.bias, xf, att.heads)
-        saved = (x, xn, mean, rstd, qkv, Mb, cx, cxs, kmax, ksum)
-    else:
-        o, cx, cxs, kmax, ksum = ops.linattn_fwd(qkv, att.heads, att.scale)
-        y = F_.conv_forward(o, att.heads * 32, att.to_out.weight, att.to_out.bias, res=xf)
-        saved = (x, xn, mean, rstd, qkv, o, cx, cxs, kmax, ksum)
-    yb = ops.to_bf16(y[..., :dim] if y.shape[-1] != dim else y, dest.second() if dest is not None else None)
-    return yb, saved
-
-
-def _attn_backward(ctx, dy):
-    norm, att = ctx.m.fn.norm, ctx.m.fn.fn
-    if dy.stride(-1) != 1:
-        dy = dy.contiguous()
-    dyf = ops.to_f32(dy)
-    if ctx.qfold:
-        x, xn, mean, rstd, kv, Mb, cx, cxs, kmax, ksum, Nb, xnb = ctx.saved_tensors
-        dim = x.shape[-1]
-        dxn, dctx, rvec = ops.linattn_fold_bwd(xn, dyf, Mb, Nb, cx, cxs, att.to_qkv.weight, att.to_out.weight, att.to_out.bias, att.heads, att.scale)
-        if ctx.kv_planes:
-            B_, H_, W_, C2 = kv.shape
-            dkv_s = (ops.new_bf(kv, B_, H_, W_, C2), None)
-            ops.linattn_bwd_core(kv, dctx, rvec, kmax, ksum, None, att.heads, koff=0, planes=dkv_s)
-            F_.kv_backward_planes(xn, (xnb, None), dim, dkv_s, att.to_qkv.weight, dxn)
-        else:
-            dkv = torch.empty(kv.shape, device=kv.device, dtype=torch.float32)
-            ops.linattn_bwd_core(kv, dctx, rvec, kmax, ksum, dkv, att.heads, koff=0)
-            F_.kv_backward(xn, dim, dkv, att.to_qkv.weight, dxn)
-    else:
-        x, xn, mean, rstd, qkv, o, cx, cxs, kmax, ksum = ctx.saved_tensors
-        dim, HD = x.shape[-1], att.heads * 32
-        if ctx.fused:
-            B, H, W, _ = qkv.shape
-            dqkv = torch.empty((B, H, W, 3 * HD), device=qkv.device, dtype=torch.float32)
-            dctx, rvec = ops.linattn_project_bwd(qkv, dyf, o, cx, cxs, att.to_out.weight, att.to_out.bias, dqkv, att.heads, att.scale)
-            ops.linattn_bwd_core(qkv, dctx, rvec, kmax, ksum, dqkv, att.heads)
-        else:
-            do = F_.conv_backward(o, HD, dyf, att.to_out.weight, att.to_out.bias)
-            dqkv = ops.linattn_bwd(qkv, do, cx, cxs, kmax, ksum, att.heads, att.scale)
-        dxn = F_.conv_backward(xn, dim, dqkv, att.to_qkv.weight, None)
-    dx = ops.layernorm_bwd_bf(dxn, x, norm.g, norm.b, mean, rstd, add=dy)     # + the residual branch, same pass; bf16 out
-    _done(ctx)
-    return None, dx, None, None
+        return F_.linattn_block_backward(ctx, dy, True)

@@ -37,7 +37,7 @@ ACT_NONE, ACT_GELU, ACT_SILU = 0, 1, 2
 
 
 def _conv_plans(kind, H, W, k, stride, pad):
-    """(fwd plan, dgrad plan, wgrad plan, packed-kind prefix, (s_r, s_c) factory) for a conv module."""
+    """(fwd plan, dgrad plan, wgrad plan) for a conv module."""
     if kind == "conv":
         pt, pl, pb, pr = pad
         return (cd.conv_fwd(H, W, k, k, stride, pt, pl, pb, pr), cd.conv_dgrad(H, W, k, k, stride, pt, pl, pb, pr),
@@ -45,17 +45,32 @@ def _conv_plans(kind, H, W, k, stride, pad):
     return cd.convT_fwd(H, W, k, k, stride, pad[0]), cd.convT_dgrad(H, W, k, k, stride, pad[0]), cd.convT_wgrad(H, W, k, k, stride, pad[0])
 
 
-def conv_forward(x, Cin, weight, bias, kind="conv", stride=1, pad=None, xs=None, split_out=False, planes_only=False, **epi):
-    """x [B,H,W,*] -> conv(x) with the weight in its PyTorch layout ([Cout,Cin,k,k] or [Cin,Cout,k,k]).
-    xs: optional pre-split (hi, lo) bf16 planes of x (see want_presplit).
-    split_out: return (y, (hi, lo) planes of y) -- fused into the epilogue on the pre-split path."""
+def conv_geom(x, weight, kind, stride, pad):
+    """(fwd plan, dgrad plan, wgrad plan, Cout, taps) of a conv module applied to x (pad = None: 'same' padding k // 2)."""
     k = weight.shape[-1]
     if pad is None:
         pad = (k // 2,) * 4
     _, H, W, _ = x.shape
-    plan = _conv_plans(kind, H, W, k, stride, pad)[0]
-    Cout = weight.shape[0] if kind == "conv" else weight.shape[1]
-    sfx = _sp_suffix(Cin * k * k, Cout)
+    return _conv_plans(kind, H, W, k, stride, pad) + (weight.shape[0] if kind == "conv" else weight.shape[1], k * k)
+
+
+def conv_param_grads(x, Cin, dy, weight, bias, kind, stride, pad, xs, dys):
+    """Accumulates a conv module's weight / bias gradients (xs / dys: optional operand planes of x / dy); returns (dgrad plan, Cout, taps)."""
+    _, pd, pw, Cout, KK = conv_geom(x, weight, kind, stride, pad)
+    s_r, s_c = (KK, Cin * KK) if kind == "conv" else (Cout * KK, KK)
+    fuse_bias = bias is not None and kind == "conv"        # dY rows stream through the wgrad kernel exactly once
+    ops.wgrad_into(ops.grad_of(weight), pw, x, Cin, dy, Cout, 1, s_r, s_c, gbias=ops.grad_of(bias) if fuse_bias else None, xa_s=xs, xb_s=dys)
+    if bias is not None and not fuse_bias:
+        ops.colsum_into(ops.grad_of(bias), dy, Cout)
+    return pd, Cout, KK
+
+
+def conv_forward(x, Cin, weight, bias, kind="conv", stride=1, pad=None, xs=None, split_out=False, planes_only=False, **epi):
+    """x [B,H,W,*] -> conv(x) with the weight in its PyTorch layout ([Cout,Cin,k,k] or [Cin,Cout,k,k]).
+    xs: optional pre-split (hi, lo) bf16 planes of x (see want_presplit).
+    split_out: return (y, (hi, lo) planes of y) -- fused into the epilogue on the pre-split path."""
+    plan, _, _, Cout, KK = conv_geom(x, weight, kind, stride, pad)
+    sfx = _sp_suffix(Cin * KK, Cout)
     wp = ops.packed(weight, ("conv_fwd" if kind == "conv" else "convT_fwd") + sfx)
     if xs is None and sfx and _ALWAYS_PRESPLIT and rt.precision != "f32" and Cin % 8 == 0 and x.device.type != "meta":
         xs = ops.split_bf16(x[..., :Cin] if x.shape[-1] != Cin else x)     # every bf16x3 GEMM goes through the LDS-DMA kernel
@@ -82,6 +97,9 @@ _AUTO_PRESPLIT = os.environ.get("CDF_AUTO_PRESPLIT", "1") != "0"
 _SP_KMIN = int(os.environ.get("CDF_SP_KMIN", "64"))     # tuning knob: smallest K routed to the bf16 matrix cores
 _LN_FUSE = os.environ.get("CDF_LN_FUSE", "1") != "0"  # conv1's data gradient runs the LayerNorm backward in its epilogue (ops.conv_dgrad_lnbwd)
 _PRE_GRAD = os.environ.get("CDF_PRE_GRAD", "0") != "0"  # conv1's epilogue stores GELU'(pre) (same erf / exp evaluation as GELU); conv2's data gradient multiplies by it
+_KV_PLANES = os.environ.get("CDF_KV_PLANES", "1") != "0"     # the k | v projection's backward on operand planes (kv_planes_ok)
+_ATTN_QFOLD = os.environ.get("CDF_ATTN_QFOLD", "1") != "0"   # q projection folded into the attention product too (dim <= heads*32)
+_ATTN_KVCTX = os.environ.get("CDF_ATTN_KVCTX", "1") != "0"   # ... with the k|v projection and the context in one kernel (ops.linattn_kvctx)
 
 
 def _sp_suffix(K, N):
@@ -97,23 +115,7 @@ def conv_backward(x, Cin, dy, weight, bias, kind="conv", stride=1, pad=None, nee
     accumulates into weight.grad / bias.grad.
     ln = (h, norm, mean, rstd): x was LayerNorm(h) -- returns (d, fused): fused True => d is already dh, the LayerNorm backward ran in the
     data-gradient GEMM's epilogue and norm.g / norm.b have their gradients; False => d is dx as usual (the caller runs ops.layernorm_bwd)."""
-    k = weight.shape[-1]
-    if pad is None:
-        pad = (k // 2,) * 4
-    _, H, W, _ = x.shape
-    _, pd, pw = _conv_plans(kind, H, W, k, stride, pad)
-    KK = k * k
-    if kind == "conv":
-        Cout = weight.shape[0]
-        s_r, s_c = KK, Cin * KK
-    else:
-        Cout = weight.shape[1]
-        s_r, s_c = Cout * KK, KK
-    fuse_bias = bias is not None and kind == "conv"        # dY rows stream through the wgrad kernel exactly once
-    ops.wgrad_into(ops.grad_of(weight), pw, x, Cin, dy, Cout, 1, s_r, s_c, gbias=ops.grad_of(bias) if fuse_bias else None,
-                   xa_s=xs, xb_s=dys)
-    if bias is not None and not fuse_bias:
-        ops.colsum_into(ops.grad_of(bias), dy, Cout)
+    pd, Cout, KK = conv_param_grads(x, Cin, dy, weight, bias, kind, stride, pad, xs, dys)
     if not need_dx:
         return None
     sfx = _sp_suffix(Cout * KK, Cin)
@@ -553,20 +555,16 @@ class ConvNextBlockFn(torch.autograd.Function):
         return None, dx, dtb, None, None
 
 
-def kv_forward(xn, dim, w_qkv):
-    """kv = xn . Wkv^T ([B,H,W,2 HD]): the k | v rows of to_qkv as a 1x1 convolution of their own (ops.linattn_fold)."""
-    N2 = w_qkv.shape[0] // 3 * 2
-    plan = _conv_plans("conv", xn.shape[1], xn.shape[2], 1, 1, (0, 0, 0, 0))[0]
-    return ops.conv_gemm(plan, xn, dim, ops.packed(w_qkv, "kv_fwd" + _sp_suffix(dim, N2)), N2)
-
-
-def kv_backward(xn, dim, dkv, w_qkv, dxn):
-    """rows HD .. 3 HD of to_qkv.weight.grad += dkv^T xn;  dxn += dkv . Wkv (dxn None: the data gradient was taken elsewhere)."""
+def kv_backward(xn, dim, dkv, w_qkv, dxn, xn_s=None):
+    """rows HD .. 3 HD of to_qkv.weight.grad += dkv^T xn;  dxn += dkv . Wkv.  With xn_s (xn's operand planes) dkv is a pair of
+    operand planes as well (kv_planes_ok) and both products are the LDS-DMA plane GEMMs."""
     HD = w_qkv.shape[0] // 3
-    _, pd, pw = _conv_plans("conv", xn.shape[1], xn.shape[2], 1, 1, (0, 0, 0, 0))
+    B, H, W, _ = xn.shape
+    _, pd, pw = _conv_plans("conv", H, W, 1, 1, (0, 0, 0, 0))
+    if xn_s is not None:
+        ops.wgrad_into(ops.grad_of(w_qkv)[HD:], pw, xn, dim, ops.shape_only(B, H, W, 2 * HD), 2 * HD, 1, 1, dim, xa_s=xn_s, xb_s=dkv)
+        return ops.conv_gemm_presplit(pd, dkv, 2 * HD, ops.packed(w_qkv, "kv_dgrad_sp"), dim, y=dxn, accumulate=1)
     ops.wgrad_into(ops.grad_of(w_qkv)[HD:], pw, xn, dim, dkv, 2 * HD, 1, 1, dim)
-    if dxn is None:
-        return None
     return ops.conv_gemm(pd, dkv, 2 * HD, ops.packed(w_qkv, "kv_dgrad" + _sp_suffix(2 * HD, dim)), dim, y=dxn, accumulate=1)
 
 
@@ -580,102 +578,103 @@ def kv_planes_ok(xn, dim, heads):
             and xn.device.type != "meta")
 
 
-def kv_backward_planes(xn, xn_s, dim, dkv_s, w_qkv, dxn):
-    """kv_backward with both operands as bf16 planes: rows HD .. 3 HD of to_qkv.weight.grad += dkv^T xn;  dxn += dkv . Wkv."""
-    HD = w_qkv.shape[0] // 3
-    B, H, W, _ = xn.shape
-    _, pd, pw = _conv_plans("conv", H, W, 1, 1, (0, 0, 0, 0))
-    ops.wgrad_into(ops.grad_of(w_qkv)[HD:], pw, xn, dim, ops.shape_only(B, H, W, 2 * HD), 2 * HD, 1, 1, dim, xa_s=xn_s, xb_s=dkv_s)
-    return ops.conv_gemm_presplit(pd, dkv_s, 2 * HD, ops.packed(w_qkv, "kv_dgrad_sp"), dim, y=dxn, accumulate=1)
-
-
-_KV_PLANES = os.environ.get("CDF_KV_PLANES", "1") != "0"
-_ATTN_QFOLD = os.environ.get("CDF_ATTN_QFOLD", "1") != "0"   # q projection folded into the attention product too (dim <= heads*32)
-_ATTN_KVCTX = os.environ.get("CDF_ATTN_KVCTX", "1") != "0"   # ... with the k|v projection and the context in one kernel (ops.linattn_kvctx)
-
-
-class LinAttnBlockFn(torch.autograd.Function):
-    """Residual(PreNorm(dim, LinearAttention(dim))) (deblurring_diffusion_pytorch.py:83-89,123-131,167-187)."""
-
-    @staticmethod
-    def forward(ctx, anchor, x, m, dest=None):
-        norm, att = m.fn.norm, m.fn.fn
-        dim = x.shape[-1]
-        grad_on = ctx.needs_input_grad[0]   # anchor: True iff autograd is recording
-        ydst = {"y": dest.second()} if dest is not None else {}      # skip tensor: produced in place in its concat buffer (CatBuf)
-        ctx.qfold_possible = dim % 4 == 0 and _ATTN_FUSED >= 1 and _ATTN_QFOLD and dim <= att.heads * 32 and att.heads <= 4
-        ctx.kv_planes = bool(grad_on and ctx.qfold_possible and kv_planes_ok(x, dim, att.heads))
-        xn_s = None
-        if ctx.kv_planes:
-            xn, mean, rstd, xn_s = ops.layernorm_fwd(x, norm.g, norm.b, norm.eps, grad_on, split_out=True)
+def linattn_block_forward(ctx, x, m, dest, bf):
+    """Residual(PreNorm(dim, LinearAttention(dim))) (deblurring_diffusion_pytorch.py:83-89,123-131,167-187) in its three arithmetic forms.
+    bf: x and the result are tensors of the bf16 stream (bf16store.LinAttnBlockBF); the block's inside is the same fp32 computation."""
+    norm, att = m.fn.norm, m.fn.fn
+    w_qkv, w_out, b_out = att.to_qkv.weight, att.to_out.weight, att.to_out.bias
+    dim, HD = x.shape[-1], att.heads * 32
+    grad_on = ctx.needs_input_grad[0]   # anchor: True iff autograd is recording
+    ydst = dest.second() if dest is not None else None          # skip tensor: produced in place in its concat buffer (CatBuf)
+    # to_out folded into the attention product where that shrinks the batched GEMMs (dim <= heads*32: the 128- and 64-pixel
+    # levels of the CelebA net); above, the per-image [HD x dim] GEMMs over a few hundred pixels are latency-bound and the
+    # plain form (K = 32 head products + a dense to_out GEMM over all images) is faster (16 x 16: 1.75 vs 2.2 ms per 12 passes)
+    foldable = _ATTN_QFOLD and dim <= HD and att.heads <= 4
+    ctx.fused = dim % 4 == 0 and (_ATTN_FUSED == 2 or (_ATTN_FUSED == 1 and dim <= HD))
+    ctx.qfold_possible = dim % (8 if bf else 4) == 0 and _ATTN_FUSED >= 1 and foldable
+    ctx.qfold = ctx.qfold_possible if bf else (ctx.fused and foldable)
+    ctx.kv_planes = bool(grad_on and ctx.qfold_possible and kv_planes_ok(x, dim, att.heads))    # k | v backward on operand planes
+    ln = (ops.layernorm_fwd_bf(x, norm.g, norm.b, norm.eps, grad_on, out_f32=True, planes=ctx.kv_planes) if bf else
+          ops.layernorm_fwd(x, norm.g, norm.b, norm.eps, grad_on, split_out=ctx.kv_planes))
+    xn, mean, rstd = ln[:3]
+    xn_s = (None, None) if not ctx.kv_planes else ((ln[3], None) if bf else ln[3])
+    ctx.m = m
+    _used(ctx, norm, att.to_qkv, att.to_out)
+    if ctx.qfold:
+        # q folded in as well: only k | v are projected, y = xn . N_b + b + x (ops.linattn_fold; on the bf16 stream the product reads the
+        # residual from it and writes its result into it: x and y cross the boundary once each, as bf16)
+        if _ATTN_KVCTX and ops.linattn_kvctx_ok(xn, dim, att.heads):
+            kv, cx, cxs, kmax, ksum = ops.linattn_kvctx(xn, dim, w_qkv, att.heads, att.scale)    # one pass: k | v never re-read
         else:
-            xn, mean, rstd = ops.layernorm_fwd(x, norm.g, norm.b, norm.eps, grad_on)
-        ctx.m = m
-        _used(ctx, norm, att.to_qkv, att.to_out)
-        # to_out folded into the attention product where that shrinks the batched GEMMs (dim <= heads*32: the 128- and 64-pixel
-        # levels of the CelebA net); above, the per-image [HD x dim] GEMMs over a few hundred pixels are latency-bound and the
-        # plain form (K = 32 head products + a dense to_out GEMM over all images) is faster (16 x 16: 1.75 vs 2.2 ms per 12 passes)
-        ctx.fused = dim % 4 == 0 and (_ATTN_FUSED == 2 or (_ATTN_FUSED == 1 and dim <= att.heads * 32))
-        ctx.qfold = ctx.fused and _ATTN_QFOLD and dim <= att.heads * 32 and att.heads <= 4
-        if ctx.qfold:
-            # q folded in as well: only k | v are projected, y = xn . N_b + b + x (ops.linattn_fold)
-            if _ATTN_KVCTX and ops.linattn_kvctx_ok(xn, dim, att.heads):
-                kv, cx, cxs, kmax, ksum = ops.linattn_kvctx(xn, dim, att.to_qkv.weight, att.heads, att.scale)    # one pass: k | v never re-read
-            else:
-                kv = kv_forward(xn, dim, att.to_qkv.weight)
-                cx, cxs, kmax, ksum = ops.linattn_context(kv, att.heads, att.scale, koff=0)
-            y, Mb, Nb = ops.linattn_fold(xn, cxs, att.to_qkv.weight, att.to_out.weight, att.to_out.bias, x, att.heads, **ydst)
-            ctx.save_for_backward(x, xn, mean, rstd, kv, Mb, cx, cxs, kmax, ksum, Nb, *(xn_s or (None, None)))
-            y._cdf_grad_f32 = True                    # (this block's backward reads its incoming gradient as fp32)
-            return y
-        qkv = conv_forward(xn, dim, att.to_qkv.weight, None)
+            plan = _conv_plans("conv", xn.shape[1], xn.shape[2], 1, 1, (0, 0, 0, 0))[0]        # the k | v rows of to_qkv as a 1x1 conv of their own
+            kv = ops.conv_gemm(plan, xn, dim, ops.packed(w_qkv, "kv_fwd" + _sp_suffix(dim, 2 * HD)), 2 * HD)
+            cx, cxs, kmax, ksum = ops.linattn_context(kv, att.heads, att.scale, koff=0)
+        y, Mb, Nb = ops.linattn_fold(xn, cxs, w_qkv, w_out, b_out, x, att.heads, y=ydst)
+        ctx.save_for_backward(x, xn, mean, rstd, kv, Mb, cx, cxs, kmax, ksum, Nb, *xn_s)
+    else:
+        # (bf16 stream, deeper levels: these forms keep an fp32 residual operand and their fp32 result is rounded into the stream)
+        res, yf = (ops.to_f32(x), None) if bf else (x, ydst)
+        qkv = conv_forward(xn, dim, w_qkv, None)
         if ctx.fused:
             # output projection folded into the attention product: the attention output is never materialised (ops.linattn_project)
             cx, cxs, kmax, ksum = ops.linattn_context(qkv, att.heads, att.scale)
-            y, Mb = ops.linattn_project(qkv, cxs, att.to_out.weight, att.to_out.bias, x, att.heads, **ydst)
-            ctx.save_for_backward(x, xn, mean, rstd, qkv, Mb, cx, cxs, kmax, ksum)
-            y._cdf_grad_f32 = True
-            return y
-        o, cx, cxs, kmax, ksum = ops.linattn_fwd(qkv, att.heads, att.scale)
-        y = conv_forward(o, att.heads * 32, att.to_out.weight, att.to_out.bias, res=x, **ydst)
+            y, o = ops.linattn_project(qkv, cxs, w_out, b_out, res, att.heads, y=yf)              # (o = Mb here)
+        else:
+            o, cx, cxs, kmax, ksum = ops.linattn_fwd(qkv, att.heads, att.scale)
+            y = conv_forward(o, HD, w_out, b_out, res=res, y=yf)
         ctx.save_for_backward(x, xn, mean, rstd, qkv, o, cx, cxs, kmax, ksum)
-        y._cdf_grad_f32 = True
-        return y
+        if bf:
+            y = ops.to_bf16(y[..., :dim] if y.shape[-1] != dim else y, ydst)
+    if not bf:
+        y._cdf_grad_f32 = True                        # (this block's backward reads its incoming gradient as fp32)
+    return y
 
-    @staticmethod
-    def backward(ctx, dy):
-        norm, att = ctx.m.fn.norm, ctx.m.fn.fn
-        if ctx.qfold:
-            x, xn, mean, rstd, kv, Mb, cx, cxs, kmax, ksum, Nb, xn_hi, xn_lo = ctx.saved_tensors
-            dim = x.shape[-1]
-            dxn, dctx, rvec = ops.linattn_fold_bwd(xn, dy, Mb, Nb, cx, cxs, att.to_qkv.weight, att.to_out.weight, att.to_out.bias,
-                                                   att.heads, att.scale)
-            if ctx.kv_planes:
-                B_, H_, W_, C2 = kv.shape
-                dkv_s = ops.split_planes_like(kv, B_, H_, W_, C2)
-                ops.linattn_bwd_core(kv, dctx, rvec, kmax, ksum, None, att.heads, koff=0, planes=dkv_s)
-                kv_backward_planes(xn, (xn_hi, xn_lo), dim, dkv_s, att.to_qkv.weight, dxn)
-            else:
-                dkv = torch.empty(kv.shape, device=kv.device, dtype=torch.float32)
-                ops.linattn_bwd_core(kv, dctx, rvec, kmax, ksum, dkv, att.heads, koff=0)
-                kv_backward(xn, dim, dkv, att.to_qkv.weight, dxn)
-            dx = ops.layernorm_bwd(dxn, x, norm.g, norm.b, mean, rstd, add=dy, planes=ops.want_grad_planes(dim))     # + the residual branch, same pass
-            _done(ctx)
-            return None, dx, None, None
+
+def linattn_block_backward(ctx, dy, bf):
+    norm, att = ctx.m.fn.norm, ctx.m.fn.fn
+    w_qkv, w_out, b_out = att.to_qkv.weight, att.to_out.weight, att.to_out.bias
+    dyf = dy
+    if bf:                                            # the incoming gradient is a bf16 tensor: widened for the fp32 inside
+        dy = dy.contiguous() if dy.stride(-1) != 1 else dy
+        dyf = ops.to_f32(dy)
+    if ctx.qfold:
+        x, xn, mean, rstd, kv, Mb, cx, cxs, kmax, ksum, Nb, xn_hi, xn_lo = ctx.saved_tensors
+        dim = x.shape[-1]
+        dxn, dctx, rvec = ops.linattn_fold_bwd(xn, dyf, Mb, Nb, cx, cxs, w_qkv, w_out, b_out, att.heads, att.scale)
+        if ctx.kv_planes:                             # dk | dv leave the attention backward kernel as operand planes
+            dkv = (ops.new_bf(kv, *kv.shape), None) if bf else ops.split_planes_like(kv, *kv.shape)
+            ops.linattn_bwd_core(kv, dctx, rvec, kmax, ksum, None, att.heads, koff=0, planes=dkv)
+        else:
+            dkv = torch.empty(kv.shape, device=kv.device, dtype=torch.float32)
+            ops.linattn_bwd_core(kv, dctx, rvec, kmax, ksum, dkv, att.heads, koff=0)
+        kv_backward(xn, dim, dkv, w_qkv, dxn, (xn_hi, xn_lo) if ctx.kv_planes else None)
+    else:
         x, xn, mean, rstd, qkv, o, cx, cxs, kmax, ksum = ctx.saved_tensors
         dim, HD = x.shape[-1], att.heads * 32
         if ctx.fused:
-            B, H, W, _ = qkv.shape
-            dqkv = torch.empty((B, H, W, 3 * HD), device=qkv.device, dtype=torch.float32)
-            dctx, rvec = ops.linattn_project_bwd(qkv, dy, o, cx, cxs, att.to_out.weight, att.to_out.bias, dqkv, att.heads, att.scale)   # (o = Mb here)
+            dqkv = torch.empty(qkv.shape[:-1] + (3 * HD,), device=qkv.device, dtype=torch.float32)
+            dctx, rvec = ops.linattn_project_bwd(qkv, dyf, o, cx, cxs, w_out, b_out, dqkv, att.heads, att.scale)   # (o = Mb here)
             ops.linattn_bwd_core(qkv, dctx, rvec, kmax, ksum, dqkv, att.heads)
         else:
-            do = conv_backward(o, HD, dy, att.to_out.weight, att.to_out.bias)
+            do = conv_backward(o, HD, dyf, w_out, b_out)
             dqkv = ops.linattn_bwd(qkv, do, cx, cxs, kmax, ksum, att.heads, att.scale)
-        dxn = conv_backward(xn, dim, dqkv, att.to_qkv.weight, None)
-        dx = ops.layernorm_bwd(dxn, x, norm.g, norm.b, mean, rstd, add=dy, planes=ops.want_grad_planes(dim))
-        _done(ctx)
-        return None, dx, None, None
+        dxn = conv_backward(xn, dim, dqkv, w_qkv, None)
+    dx = (ops.layernorm_bwd_bf(dxn, x, norm.g, norm.b, mean, rstd, add=dy) if bf else             # + the residual branch, same pass
+          ops.layernorm_bwd(dxn, x, norm.g, norm.b, mean, rstd, add=dy, planes=ops.want_grad_planes(dim)))
+    _done(ctx)
+    return None, dx, None, None
+
+
+class LinAttnBlockFn(torch.autograd.Function):
+    """Residual(PreNorm(dim, LinearAttention(dim))) on fp32 tensors."""
+
+    @staticmethod
+    def forward(ctx, anchor, x, m, dest=None):
+        return linattn_block_forward(ctx, x, m, dest, False)
+
+    @staticmethod
+    def backward(ctx, dy):
+        return linattn_block_backward(ctx, dy, False)
 
 
 # ===================================================================================================

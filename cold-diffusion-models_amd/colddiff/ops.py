@@ -42,29 +42,28 @@ def new_feat(ref, B, H, W, C, zero=False):
 # ---------------------------------------------------------------------------------------------------
 # packed-weight cache
 # ---------------------------------------------------------------------------------------------------
-_pack_cache = {}          # (id(param), kind) -> [key, out, weakref, geom, last_used_epoch]
+_pack_cache = {}          # (id(param), kind) -> _Packed
 _pack_tables = {}         # device -> (signature, device table tensor, nentries, nblocks): the cdf_pack_many descriptor table
-_PACK_ALL = __import__("os").environ.get("CDF_PACK_ALL", "1") != "0"
+_PACK_ALL = os.environ.get("CDF_PACK_ALL", "1") != "0"
 # smallest pixel count whose weight gradient runs on the bf16 matrix cores (below, the fp32-MFMA kernel; 2048 until the end of round 2:
 # the 4 x 4-pixel level of the 32 x 32 configurations is M = 512 with 512 -> 1024 channels, 62 -> 28 us per launch)
-WGRAD_SP_MIN_M = int(__import__("os").environ.get("CDF_WGRAD_SP_MIN_M", "512"))
-_SP_WGRAD_MIN_PIX = int(__import__("os").environ.get("CDF_SP_WGRAD_MIN_PIX", "128"))   # smallest pixel count per split of the in-kernel-split weight gradient
-_ATTN_KV_FUSED = __import__("os").environ.get("CDF_ATTN_KV_FUSED", "1") != "0"    # one-kernel k / v attention backward (k_attn.hip)
+WGRAD_SP_MIN_M = int(os.environ.get("CDF_WGRAD_SP_MIN_M", "512"))
+_SP_WGRAD_MIN_PIX = int(os.environ.get("CDF_SP_WGRAD_MIN_PIX", "128"))   # smallest pixel count per split of the in-kernel-split weight gradient
+_ATTN_KV_FUSED = os.environ.get("CDF_ATTN_KV_FUSED", "1") != "0"    # one-kernel k / v attention backward (k_attn.hip)
 
 
-def _pack(src, T, R, C, s_t, s_r, s_c):
-    dst = torch.empty((T, R, r4(C)), device=src.device, dtype=torch.float32)
-    rt.lib().cdf_pack_weight(P(src), P(dst), T, R, C, r4(C), s_t, s_r, s_c, rt.stream(src))
-    return dst
+class _Packed:
+    """One cached layout: `out` was packed from the parameter `ref()` when it sat at `ptr` with version counter `version`, in weights
+    epoch `epoch` and arithmetic mode `precision`; `geom` = its _pack_geom (None: cin4), `last_used` = the last epoch that asked for it."""
+    __slots__ = ("ptr", "version", "epoch", "precision", "out", "ref", "geom", "last_used")
+
+    def __init__(self, ptr, version, epoch, precision, out, ref, geom):
+        self.ptr, self.version, self.epoch, self.precision = ptr, version, epoch, precision
+        self.out, self.ref, self.geom, self.last_used = out, ref, geom, epoch
 
 
 def _pack_geom(w, kind):
     """(T, R, C, ldc, s_t, s_r, s_c, bf16, off) of dst[t][r][c] = src[off + c*s_c + r*s_r + t*s_t] for a GEMM layout of parameter w, or None."""
-    g = _pack_geom0(w, kind)
-    return g if (g is None or len(g) == 9) else g + (0,)
-
-
-def _pack_geom0(w, kind):
     if kind.startswith("kv_"):
         # the k | v rows of a LinearAttention to_qkv weight [3 HD, Ci, 1, 1] as a conv of its own (rows HD .. 3 HD)
         Co3, Ci = w.shape[0], w.shape[1]
@@ -82,11 +81,11 @@ def _pack_geom0(w, kind):
     if kind in ("conv_fwd", "conv_dgrad"):
         Co, Ci, KH, KW = w.shape
         KK = KH * KW
-        return (KK, Ci, Co, r4(Co), 1, KK, Ci * KK, False) if kind == "conv_fwd" else (KK, Co, Ci, r4(Ci), 1, Ci * KK, KK, False)
+        return (KK, Ci, Co, r4(Co), 1, KK, Ci * KK, False, 0) if kind == "conv_fwd" else (KK, Co, Ci, r4(Ci), 1, Ci * KK, KK, False, 0)
     if kind in ("convT_fwd", "convT_dgrad"):
         Ci, Co, KH, KW = w.shape
         KK = KH * KW
-        return (KK, Ci, Co, r4(Co), 1, Co * KK, KK, False) if kind == "convT_fwd" else (KK, Co, Ci, r4(Ci), 1, KK, Co * KK, False)
+        return (KK, Ci, Co, r4(Co), 1, Co * KK, KK, False, 0) if kind == "convT_fwd" else (KK, Co, Ci, r4(Ci), 1, KK, Co * KK, False, 0)
     if kind in ("conv_fwd_sp", "conv_dgrad_sp", "convT_fwd_sp", "convT_dgrad_sp"):
         # bf16 hi/lo planes [KK][N][ldk] (K contiguous) for the split-precision kernels
         if kind.startswith("convT"):
@@ -98,16 +97,16 @@ def _pack_geom0(w, kind):
             Co, Ci, KH, KW = w.shape
             KK = KH * KW
             N, K, s_n, s_k = (Co, Ci, Ci * KK, KK) if kind == "conv_fwd_sp" else (Ci, Co, KK, Ci * KK)
-        return (KK, N, K, (K + 31) // 32 * 32, 1, s_n, s_k, True)
+        return (KK, N, K, (K + 31) // 32 * 32, 1, s_n, s_k, True, 0)
     if kind == "cin_z":
         # [1][Cout][9 Cin]: the 3x3 weight as the [K = Cout][N = Cin 9] matrix of the two-stage small-Cin data gradient (conv_cin_dgrad2)
         Co, Ci, KH, KW = w.shape
-        return (1, Co, Ci * KH * KW, r4(Ci * KH * KW), 0, Ci * KH * KW, 1, False)
+        return (1, Co, Ci * KH * KW, r4(Ci * KH * KW), 0, Ci * KH * KW, 1, False, 0)
     if kind == "dw":
-        return (49, 1, w.shape[0], r4(w.shape[0]), 1, 0, 49, False)
+        return (49, 1, w.shape[0], r4(w.shape[0]), 1, 0, 49, False, 0)
     if kind == "lin_fwd":
         N, K = w.shape
-        return (1, K, N, r4(N), 0, 1, K, False)
+        return (1, K, N, r4(N), 0, 1, K, False, 0)
     return None
 
 
@@ -142,20 +141,19 @@ def _repack_all(device, epoch_used):
     import struct
     L = rt.lib()
     ents = []
-    for slot, ent in list(_pack_cache.items()):
-        key, out, ref, geom, used = ent
-        p = ref()
-        if p is None or geom is None or used != epoch_used or key[2] != epoch_used or p.device != device:
+    for e in list(_pack_cache.values()):
+        p = e.ref()
+        if p is None or e.geom is None or e.last_used != epoch_used or e.epoch != epoch_used or p.device != device:
             continue
-        if key[0] != p.data_ptr() or key[1] != p._version or key[4] != rt.precision:
+        if e.ptr != p.data_ptr() or e.version != p._version or e.precision != rt.precision:
             continue                                         # re-homed / rewritten through torch / other arithmetic mode: individual path
-        ents.append((slot, ent, p))
+        ents.append((e, p))
     if len(ents) < 2:
         return 0
     recs, first, sig = [], 0, []
-    for slot, ent, p in ents:
-        T, R, C, ldc, s_t, s_r, s_c, bf16, off = ent[3]
-        out = ent[1]
+    for e, p in ents:
+        T, R, C, ldc, s_t, s_r, s_c, bf16, off = e.geom
+        out = e.out
         d0, d1 = (P(out[0]), P(out[1])) if bf16 else (P(out), 0)
         recs.append(struct.pack("<QQQqqqiiiiii", p.data_ptr() + 4 * off, d0, d1, s_t, s_r, s_c, T, R, C, ldc, 1 if bf16 else 0, first))
         sig.append((p.data_ptr() + 4 * off, d0, d1))
@@ -168,9 +166,8 @@ def _repack_all(device, epoch_used):
         t = torch.frombuffer(bytearray(blob), dtype=torch.uint8).to(device)
         tab = _pack_tables[device] = (sig, t, len(recs), first)
     L.cdf_pack_many(P(tab[1]), tab[2], tab[3], rt.stream(tab[1]))
-    for slot, ent, p in ents:
-        k = ent[0]
-        ent[0] = (k[0], k[1], rt.weights_epoch, k[3], k[4])
+    for e, p in ents:
+        e.epoch = rt.weights_epoch
     return len(ents)
 
 
@@ -186,24 +183,23 @@ def packed(param, kind):
     When only the weights epoch moved (an optimizer step rewrote the arena), the first request re-packs EVERY layout the previous
     epoch used in one cdf_pack_many launch, in place.
     """
-    key = (param.data_ptr(), param._version, rt.weights_epoch, kind, rt.precision)
+    epoch = rt.weights_epoch
     slot = (id(param), kind)
     hit = _pack_cache.get(slot)
-    if hit is not None and hit[2]() is param:                # the weakref guards against id()/address reuse by a new tensor
-        if hit[0] == key:
-            hit[4] = rt.weights_epoch
-            return hit[1]
-        k = hit[0]
-        if (_PACK_ALL and hit[3] is not None and k[0] == key[0] and k[1] == key[1] and k[4] == key[4] and param.device.type != "meta"
-                and hit[4] == k[2]):
-            if _repack_all(param.device, k[2]) and hit[0] == key:
-                hit[4] = rt.weights_epoch
-                return hit[1]
+    if hit is not None and hit.ref() is not param:           # the weakref guards against id()/address reuse by a new tensor
+        hit = None
+    if hit is not None and hit.ptr == param.data_ptr() and hit.version == param._version and hit.precision == rt.precision:
+        if hit.epoch != epoch and _PACK_ALL and hit.geom is not None and param.device.type != "meta" and hit.last_used == hit.epoch:
+            _repack_all(param.device, hit.epoch)             # (moves hit.epoch to this epoch if it refreshed this layout too)
+        if hit.epoch == epoch:
+            hit.last_used = epoch
+            return hit.out
     w = param.detach()
     geom = _pack_geom(w, kind) if kind != "cin4" else None
-    reuse = hit[1] if (hit is not None and hit[2]() is param and hit[3] == geom and geom is not None) else None
+    reuse = hit.out if (hit is not None and hit.geom == geom and geom is not None) else None
     out = _pack_one(w, kind, geom, reuse)
-    _pack_cache[slot] = [key, out, weakref.ref(param, lambda _r, slot=slot: _pack_cache.pop(slot, None)), geom, rt.weights_epoch]
+    ref = weakref.ref(param, lambda _r, slot=slot: _pack_cache.pop(slot, None))
+    _pack_cache[slot] = _Packed(param.data_ptr(), param._version, epoch, rt.precision, out, ref, geom)
     return out
 
 
@@ -287,40 +283,49 @@ def split_planes_like(ref, B, H, W, C):
             f((B, H, W, ld), device=ref.device, dtype=torch.int16) if rt.precision == "bf16x3" else None)
 
 
+def _gemm_bf16x(plan, x_hi, x_lo, ldx, wp, Cin, Cout, y, ldy, ys, ld_ys, bias, sbias, res, pre, mul, act, mul_mode, accumulate, io):
+    """The one call path of the pre-split GEMM (include/colddiff.h): x_hi / x_lo = the operand planes (pitch ldx), wp = (hi, lo) packed
+    weights, y = the fp32 output or None (pitch ldy), ys = (hi, lo) output planes (pitch ld_ys).  io = None: cdf_conv_gemm_bf16x (fp32
+    epilogue operands); else the io_bf16 bits of cdf_conv_gemm_bf16x_io."""
+    L, dev, B = rt.lib(), x_hi.device, x_hi.shape[0]
+    ldv = lambda t: 0 if t is None else ld_of(t)
+    # grids far below one tile per CU (a few hundred pixels): split-K through a workspace (include/colddiff.h)
+    M = B * plan.QH * plan.QW
+    ws, nws = None, 0
+    if M <= 4096 and dev.type != "meta":
+        ks = L.cdf_conv_gemm_bf16x_ksplit(M, Cout, plan.nphase, plan.desc[2], rt.tune_ptr())
+        if ks > 1:
+            nws = ks * M * r4(Cout)
+            ws = torch.empty((nws,), device=dev, dtype=torch.float32)
+    if io is None:
+        L.cdf_conv_gemm_bf16x(P(x_hi), P(x_lo), ldx, P(zero_page(dev)), P(wp[0]), P(wp[1]), wp[0].shape[-1], P(y), ldy,
+                              B, plan.H, plan.W, Cin, plan.OH, plan.OW, Cout, plan.QH, plan.QW, plan.os, plan.istride, plan.nphase,
+                              plan.desc, P(bias), P(sbias), 0 if sbias is None else sbias.stride(0), P(res), ldv(res), P(pre),
+                              ldv(pre), P(mul), ldv(mul), act, mul_mode, accumulate, P(ys[0]), P(ys[1]), ld_ys, P(ws), nws,
+                              rt.tune_ptr(), rt.stream(x_hi))
+    else:
+        L.cdf_conv_gemm_bf16x_io(P(x_hi), P(x_lo), ldx, P(zero_page(dev)), P(wp[0]), P(wp[1]), wp[0].shape[-1], P(y), ldy,
+                                 B, plan.H, plan.W, Cin, plan.OH, plan.OW, Cout, plan.QH, plan.QW, plan.os, plan.istride, plan.nphase,
+                                 plan.desc, P(bias), P(sbias), 0 if sbias is None else sbias.stride(0), P(res), ldv(res), P(pre),
+                                 ldv(pre), P(mul), ldv(mul), act, mul_mode, accumulate, io, P(ys[0]), P(ys[1]), ld_ys, P(ws), nws,
+                                 rt.tune_ptr(), rt.stream(x_hi))
+
+
 def conv_gemm_presplit(plan, xs, Cin, wp, Cout, y=None, bias=None, sbias=None, res=None, pre=None, mul=None, act=0, mul_mode=0,
                        accumulate=0, split_out=False, planes_only=False, pre_grad=False):
     """conv_gemm with the activation already split into bf16 hi/lo planes (xs) and (hi, lo) packed weights (wp).
     split_out: also return the output's own (hi, lo) planes, written by the same epilogue (fused cdf_split_bf16).
-    planes_only (with split_out): do not materialise the fp32 output at all (a shape_only stand-in is returned)."""
+    planes_only (with split_out): do not materialise the fp32 output at all (a shape_only stand-in is returned).
+    pre_grad: `pre` receives GELU'(v) out of the activation's own erf / exp evaluation (the backward multiplies by it: mul_mode 3)."""
     hi, lo = xs
     B = hi.shape[0]
     planes_only = planes_only and split_out and Cout % 4 == 0 and y is None and not accumulate
     ys = split_planes_like(hi, B, plan.OH, plan.OW, Cout) if (split_out and Cout % 4 == 0) else None
     if y is None:
         y = shape_only(B, plan.OH, plan.OW, Cout) if planes_only else new_feat(hi, B, plan.OH, plan.OW, Cout)
-    ldv = lambda t: 0 if t is None else ld_of(t)
-    # grids far below one tile per CU (a few hundred pixels): split-K through a workspace (include/colddiff.h)
-    M = B * plan.QH * plan.QW
-    ws, nws = None, 0
-    if M <= 4096 and hi.device.type != "meta":
-        ks = rt.lib().cdf_conv_gemm_bf16x_ksplit(M, Cout, plan.nphase, plan.desc[2], rt.tune_ptr())
-        if ks > 1:
-            nws = ks * M * r4(Cout)
-            ws = torch.empty((nws,), device=hi.device, dtype=torch.float32)
-    if pre_grad:
-        # `pre` receives GELU'(v) out of the activation's own erf / exp evaluation (the backward multiplies by it: mul_mode 3)
-        assert pre is not None and act in (1, 2)
-        rt.lib().cdf_conv_gemm_bf16x_io(P(hi), P(lo), hi.shape[-1], P(zero_page(hi.device)), P(wp[0]), P(wp[1]), wp[0].shape[-1], P(y), ld_of(y),
-                                        B, plan.H, plan.W, Cin, plan.OH, plan.OW, Cout, plan.QH, plan.QW, plan.os, plan.istride, plan.nphase,
-                                        plan.desc, P(bias), P(sbias), 0 if sbias is None else sbias.stride(0), P(res), ldv(res), P(pre),
-                                        ldv(pre), P(mul), ldv(mul), act, mul_mode, accumulate, IO_PRE_GRAD, P(ys[0]) if ys else 0,
-                                        P(ys[1]) if ys else 0, ys[0].shape[-1] if ys else 0, P(ws), nws, rt.tune_ptr(), rt.stream(hi))
-    else:
-        rt.lib().cdf_conv_gemm_bf16x(P(hi), P(lo), hi.shape[-1], P(zero_page(hi.device)), P(wp[0]), P(wp[1]), wp[0].shape[-1], P(y), ld_of(y),
-                                     B, plan.H, plan.W, Cin, plan.OH, plan.OW, Cout, plan.QH, plan.QW, plan.os, plan.istride, plan.nphase,
-                                     plan.desc, P(bias), P(sbias), 0 if sbias is None else sbias.stride(0), P(res), ldv(res), P(pre),
-                                     ldv(pre), P(mul), ldv(mul), act, mul_mode, accumulate, P(ys[0]) if ys else 0, P(ys[1]) if ys else 0,
-                                     ys[0].shape[-1] if ys else 0, P(ws), nws, rt.tune_ptr(), rt.stream(hi))
+    assert not pre_grad or (pre is not None and act in (1, 2))
+    _gemm_bf16x(plan, hi, lo, hi.shape[-1], wp, Cin, Cout, y, ld_of(y), ys or (None, None), ys[0].shape[-1] if ys else 0,
+                bias, sbias, res, pre, mul, act, mul_mode, accumulate, IO_PRE_GRAD if pre_grad else None)
     if split_out:
         return y, (ys if ys is not None else split_bf16(y))
     return y
@@ -596,31 +601,65 @@ def dwconv7_wgrad(x, dy, w_param, b_param, want_dsb, dsb_out=None):
     return dsb
 
 
+def _one_tap(n):
+    return cd.conv_fwd(1, n, 1, 1, 1, 0, 0, 0, 0)
+
+
+def _bgemm(S, a, lda, w, ldw, y, ldy, n, K, N, bias=None, res=None, b_trans=0, batch=1, a_bs=0, w_bs=0, y_bs=0,
+           batch2=1, a_bs2=0, w_bs2=0, y_bs2=0, io=0, y_bf=0, ld_ys=0):
+    """batch x batch2 one-tap GEMMs in one launch: y[z] = a[z] ([n x K], pitch lda) . w[z] ([K x ldw >= N], or with b_trans a plain
+    [N x ldw >= K] matrix) + bias + res, z = outer * batch2 + inner with the element strides *_bs (outer) / *_bs2 (inner).  a, w, y, y_bf
+    are ADDRESSES (callers offset them by channels); bias / res tensors.  y_bf (with io = the io_bf16 bits of res): the result goes out
+    as a bf16 plane of pitch ld_ys instead (cdf_conv_gemm_io).  The only place that writes down the batched form of the GEMM ABI."""
+    L, desc, ldr = rt.lib(), _one_tap(n).desc, 0 if res is None else ld_of(res)
+    if y_bf:
+        L.cdf_conv_gemm_io(a, lda, w, ldw, y, ldy, 1, 1, n, K, 1, n, N, 1, n, 1, 1, 1, desc, P(bias), 0, 0, P(res), ldr, 0, 0, 0, 0, 0, 0, 0,
+                           b_trans, batch, a_bs, w_bs, y_bs, batch2, a_bs2, w_bs2, y_bs2, io, y_bf, ld_ys, S)
+    else:
+        L.cdf_conv_gemm(a, lda, w, ldw, y, ldy, 1, 1, n, K, 1, n, N, 1, n, 1, 1, 1, desc, P(bias), 0, 0, P(res), ldr, 0, 0, 0, 0, 0, 0, 0,
+                        b_trans, batch, a_bs, w_bs, y_bs, batch2, a_bs2, w_bs2, y_bs2, S)
+
+
+def _bwgrad(S, wplan, xa, lda, xb, ldb, ws, ldo, B, CA, CB, nsplit, batch=1, a_bs=0, b_bs=0, o_bs=0, bsum=None):
+    """The exact-fp32 weight-gradient GEMM in its batched form (include/colddiff.h: cdf_conv_wgrad): ws[split][..] = xa^T xb per batch entry."""
+    rt.lib().cdf_conv_wgrad(P(xa), lda, P(xb), ldb, P(ws), ldo, B, wplan.QH, wplan.QW, wplan.HA, wplan.WA, wplan.sa, wplan.HB, wplan.WB,
+                            wplan.sb, CA, CB, wplan.ntaps, wplan.desc, nsplit, batch, a_bs, b_bs, o_bs, P(bsum), S)
+
+
 def _head_gemm(x, x_off, w, out, out_off, B, n, heads, b_trans):
     """out[b, :, out_off + h*32 + j] = sum_k x[b, :, x_off + h*32 + k] * (w[b,h,k,j] | w[b,h,j,k] if b_trans),
-    one batched K=32 GEMM per head (batch = B)."""
-    L, S = rt.lib(), rt.stream(x)
-    plan = _one_tap(n)
+    one batched K=32 GEMM per head (batch = B) in one launch: blockIdx.z = b * heads + h."""
     ldx, ldo = ld_of(x), ld_of(out)
-    # one launch: blockIdx.z = b * heads + h
-    L.cdf_conv_gemm(P(x) + 4 * x_off, ldx, P(w), 32, P(out) + 4 * out_off, ldo, 1, 1, n, 32, 1, n, 32, 1, n, 1, 1, 1, plan.desc,
-                    0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1 if b_trans else 0, B, n * ldx, heads * 1024, n * ldo, heads, 32, 1024, 32, S)
+    _bgemm(rt.stream(x), P(x) + 4 * x_off, ldx, P(w), 32, P(out) + 4 * out_off, ldo, n, 32, 32, b_trans=1 if b_trans else 0,
+           batch=B, a_bs=n * ldx, w_bs=heads * 1024, y_bs=n * ldo, batch2=heads, a_bs2=32, w_bs2=1024, y_bs2=32)
+
+
+def _context_buffers(dev, B, heads):
+    """(ctx, ctxs [B, heads, 32, 32], kmax, ksum [B, heads*32]) for the context kernels to fill."""
+    ctx = torch.empty((B, heads, 32, 32), device=dev, dtype=torch.float32)
+    return (ctx, torch.empty_like(ctx), torch.empty((B, heads * 32), device=dev, dtype=torch.float32),
+            torch.empty((B, heads * 32), device=dev, dtype=torch.float32))
+
+
+def linattn_context(qkv, heads, scale, koff=None):
+    """(ctx, ctxs = scale * ctx, kmax, ksum) of LinearAttention (no output product).  koff: channel offset of k in qkv's rows
+    (default heads*32: the (q|k|v) tensor; 0 for a (k|v) tensor)."""
+    L = rt.lib()
+    B, H, W, _ = qkv.shape
+    n, HD = H * W, heads * 32
+    koff = HD if koff is None else koff
+    ctx, ctxs, kmax, ksum = _context_buffers(qkv.device, B, heads)
+    ws = torch.empty((L.cdf_linattn_ws_floats(B, n, heads),), device=qkv.device, dtype=torch.float32)
+    L.cdf_linattn_context(P(qkv), ld_of(qkv), koff, P(ctx), P(ctxs), P(kmax), P(ksum), P(ws), B, n, heads, scale, 1, rt.stream(qkv))
+    return ctx, ctxs, kmax, ksum
 
 
 def linattn_fwd(qkv, heads, scale):
     """LinearAttention core: returns (out [B,H,W,HD], ctx, ctxs, kmax, ksum)."""
-    L = rt.lib()
     B, H, W, _ = qkv.shape
-    n, HD = H * W, heads * 32
-    dev = qkv.device
-    out = torch.empty((B, H, W, HD), device=dev, dtype=torch.float32)
-    ctx = torch.empty((B, heads, 32, 32), device=dev, dtype=torch.float32)
-    ctxs = torch.empty_like(ctx)
-    kmax = torch.empty((B, HD), device=dev, dtype=torch.float32)
-    ksum = torch.empty((B, HD), device=dev, dtype=torch.float32)
-    ws = torch.empty((L.cdf_linattn_ws_floats(B, n, heads),), device=dev, dtype=torch.float32)
-    L.cdf_linattn_context(P(qkv), ld_of(qkv), HD, P(ctx), P(ctxs), P(kmax), P(ksum), P(ws), B, n, heads, scale, 1, rt.stream(qkv))
-    _head_gemm(qkv, 0, ctxs, out, 0, B, n, heads, False)          # out = q . (scale*ctx)
+    ctx, ctxs, kmax, ksum = linattn_context(qkv, heads, scale)
+    out = torch.empty((B, H, W, heads * 32), device=qkv.device, dtype=torch.float32)
+    _head_gemm(qkv, 0, ctxs, out, 0, B, H * W, heads, False)      # out = q . (scale*ctx)
     return out, ctx, ctxs, kmax, ksum
 
 
@@ -628,24 +667,14 @@ def linattn_bwd(qkv, dout, ctx, ctxs, kmax, ksum, heads, scale):
     L = rt.lib()
     B, H, W, _ = qkv.shape
     n, HD = H * W, heads * 32
-    dev, S = qkv.device, rt.stream(qkv)
+    dev = qkv.device
     dqkv = torch.empty((B, H, W, 3 * HD), device=dev, dtype=torch.float32)
     dctx = torch.empty_like(ctx)
     rvec = torch.empty((B, HD), device=dev, dtype=torch.float32)
     ws = torch.empty((L.cdf_linattn_ws_floats(B, n, heads),), device=dev, dtype=torch.float32)
-    L.cdf_linattn_dcontext(P(qkv), ld_of(qkv), P(dout), ld_of(dout), P(ctx), P(dctx), P(rvec), P(ws), B, n, heads, scale, S)
-    if _ATTN_KV_FUSED and heads <= 4:
-        _head_gemm(dout, 0, ctxs, dqkv, 0, B, n, heads, True)      # dq[n,d] = sum_e dout[n,e] ctxs[d,e]
-        L.cdf_linattn_bwd_kv(P(qkv), ld_of(qkv), HD, P(dctx), P(rvec), P(kmax), P(ksum), P(dqkv), ld_of(dqkv), HD, B, n, heads, S)
-        return dqkv
-    pn = torch.empty((B, H, W, HD), device=dev, dtype=torch.float32)
-    dp = torch.empty((B, H, W, HD), device=dev, dtype=torch.float32)
-    L.cdf_linattn_softk(P(qkv), ld_of(qkv), P(kmax), P(ksum), P(pn), HD, B, n, heads, S)
+    L.cdf_linattn_dcontext(P(qkv), ld_of(qkv), P(dout), ld_of(dout), P(ctx), P(dctx), P(rvec), P(ws), B, n, heads, scale, rt.stream(qkv))
     _head_gemm(dout, 0, ctxs, dqkv, 0, B, n, heads, True)          # dq[n,d] = sum_e dout[n,e] ctxs[d,e]
-    _head_gemm(qkv, 2 * HD, dctx, dp, 0, B, n, heads, True)        # dP[n,d] = sum_e v[n,e] dctx[d,e]
-    _head_gemm(pn, 0, dctx, dqkv, 2 * HD, B, n, heads, False)      # dv[n,e] = sum_d P[n,d] dctx[d,e]
-    L.cdf_linattn_dk(P(pn), HD, P(dp), HD, P(rvec), P(dqkv) + 4 * HD, 3 * HD, B, n, heads, S)
-    return dqkv
+    return linattn_bwd_core(qkv, dctx, rvec, kmax, ksum, dqkv, heads, koff=HD)
 
 
 # -- linear attention with the output projection folded in (round 2) ---------------------------------------------------
@@ -662,49 +691,63 @@ def _headsplit_plan(heads):
 _HEADSPLIT = {}
 
 
+def _out_matrix(ctxs, w_out, S):
+    """M_b[h*32 + d][c] = sum_e ctxs[b,h][d][e] W_out[c][h*32 + e] ([B][HD][r4(dim)]): B x heads GEMMs of 32 x 32 x dim."""
+    B, heads = ctxs.shape[0], ctxs.shape[1]
+    wp = packed(w_out, "conv_fwd")                            # [1][HD][r4(dim)]: row h*32 + e = W_out[:, h*32 + e]
+    ldw = wp.shape[-1]
+    Mb = torch.empty((B, heads * 32, ldw), device=ctxs.device, dtype=torch.float32)
+    _bgemm(S, P(ctxs), 32, P(wp), ldw, P(Mb), ldw, 32, 32, w_out.shape[0], batch=B, a_bs=heads * 1024, y_bs=heads * 32 * ldw,
+           batch2=heads, a_bs2=1024, w_bs2=32 * ldw, y_bs2=32 * ldw)
+    return Mb
+
+
 def linattn_project(qkv, ctxs, w_out, b_out, res, heads, y=None):
     """y = q . M_b + b_out + res,  M_b = blockdiag(ctxs[b]) . W_out^T.  Returns (y, Mb).  y: optional destination (a channel slice of a
     wider buffer is fine)."""
-    L, S = rt.lib(), rt.stream(qkv)
+    S = rt.stream(qkv)
     B, H, W, _ = qkv.shape
     n, HD, dim = H * W, heads * 32, w_out.shape[0]
-    wp = packed(w_out, "conv_fwd")                            # [1][HD][r4(dim)]: row h*32 + e = W_out[:, h*32 + e]
-    ldw = wp.shape[-1]
-    Mb = torch.empty((B, HD, ldw), device=qkv.device, dtype=torch.float32)
-    # M_b[h*32 + d][c] = sum_e ctxs[b,h][d][e] W_out[c][h*32 + e]: B x heads GEMMs of 32 x 32 x dim
-    L.cdf_conv_gemm(P(ctxs), 32, P(wp), ldw, P(Mb), ldw, 1, 1, 32, 32, 1, 32, dim, 1, 32, 1, 1, 1, _one_tap(32).desc,
-                    0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, B, heads * 1024, 0, HD * ldw, heads, 1024, 32 * ldw, 32 * ldw, S)
+    Mb = _out_matrix(ctxs, w_out, S)
+    ldw = Mb.shape[-1]
     if y is None:
         y = new_feat(qkv, B, H, W, dim)
     ldq, ldy = ld_of(qkv), ld_of(y)
     # y[b] = q[b] . M_b (+ bias + residual): one GEMM per image, K = HD
-    L.cdf_conv_gemm(P(qkv), ldq, P(Mb), ldw, P(y), ldy, 1, 1, n, HD, 1, n, dim, 1, n, 1, 1, 1, _one_tap(n).desc,
-                    P(b_out), 0, 0, P(res), 0 if res is None else ld_of(res), 0, 0, 0, 0, 0, 0, 0, 0, B, n * ldq, HD * ldw, n * ldy, 1, 0, 0, 0, S)
+    _bgemm(S, P(qkv), ldq, P(Mb), ldw, P(y), ldy, n, HD, dim, bias=b_out, res=res, batch=B, a_bs=n * ldq, w_bs=HD * ldw, y_bs=n * ldy)
     return y, Mb
+
+
+def _image_wgrad(xa, CA, dy, dim, ldw, b_out, S):
+    """dM[b] = xa[b]^T dy[b] ([B][CA][ldw]): per-image weight-gradient GEMM over the n pixels, split-K slabs laid out [split][b] and summed
+    in one pass; accumulates b_out's gradient = the column sums of dy as it streams by."""
+    L = rt.lib()
+    B, H, W, _ = xa.shape
+    n, dev = H * W, xa.device
+    lda, lddy = ld_of(xa), ld_of(dy)
+    tiles = (1 if CA <= 64 else (CA + 127) // 128) * (1 if dim <= 64 else (dim + 127) // 128) * B
+    ns = best_nsplit(tiles, 1024, max(1, n // 256))
+    ws = torch.empty((ns, B, CA, ldw), device=dev, dtype=torch.float32)
+    bsum = torch.empty((B * ns, ldw), device=dev, dtype=torch.float32) if b_out is not None else None
+    _bwgrad(S, cd.conv_wgrad(1, n, 1, 1, 1, 0, 0, 0, 0), xa, lda, dy, lddy, ws, ldw, 1, CA, dim, ns, batch=B, a_bs=n * lda, b_bs=n * lddy,
+            o_bs=-1, bsum=bsum)
+    dM = torch.empty((B, CA, ldw), device=dev, dtype=torch.float32)
+    L.cdf_unpack_reduce(P(ws), P(dM), ns, B, CA, dim, ldw, CA * ldw, ldw, 1, 0, 1, S)
+    if b_out is not None:
+        L.cdf_unpack_reduce(P(bsum), P(grad_of(b_out)), B * ns, 1, 1, dim, ldw, 0, 0, 1, 1, 1, S)
+    return dM
 
 
 def linattn_project_bwd(qkv, dy, Mb, ctx, ctxs, w_out, b_out, dqkv, heads, scale):
     """Backward of linattn_project: writes dq into dqkv[..., :HD], accumulates the to_out weight / bias gradients, returns
     (dctx, rvec) -- the gradient w.r.t. the (unscaled) context and rvec[b, h*32+d] = sum_e dctx*ctx for the softmax backward."""
-    L, S = rt.lib(), rt.stream(qkv)
+    S = rt.stream(qkv)
     B, H, W, _ = qkv.shape
     n, HD, dim = H * W, heads * 32, w_out.shape[0]
-    ldw, ldq, lddy, lddq = Mb.shape[-1], ld_of(qkv), ld_of(dy), ld_of(dqkv)
-    dev = qkv.device
+    ldw, lddy, lddq = Mb.shape[-1], ld_of(dy), ld_of(dqkv)
     # dq[b] = dy[b] . M_b^T  (b_trans: M_b is a plain [HD][ldw >= dim] matrix)
-    L.cdf_conv_gemm(P(dy), lddy, P(Mb), ldw, P(dqkv), lddq, 1, 1, n, dim, 1, n, HD, 1, n, 1, 1, 1, _one_tap(n).desc,
-                    0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, B, n * lddy, HD * ldw, n * lddq, 1, 0, 0, 0, S)
-    # dM_b = q[b]^T dy[b]: per-image weight-gradient GEMM over the n pixels, split-K slabs laid out [split][b] and summed in one pass
-    wplan = cd.conv_wgrad(1, n, 1, 1, 1, 0, 0, 0, 0)
-    tiles = ((HD + 127) // 128) * (1 if dim <= 64 else (dim + 127) // 128) * B
-    ns = best_nsplit(tiles, 1024, max(1, n // 256))
-    ws = torch.empty((ns, B, HD, ldw), device=dev, dtype=torch.float32)
-    bsum = torch.empty((B * ns, ldw), device=dev, dtype=torch.float32) if b_out is not None else None    # column sums of dy as it streams by
-    L.cdf_conv_wgrad(P(qkv), ldq, P(dy), lddy, P(ws), ldw, 1, 1, n, 1, n, 1, 1, n, 1, HD, dim, 1, wplan.desc, ns, B, n * ldq, n * lddy, -1, P(bsum), S)
-    dMb = torch.empty((B, HD, ldw), device=dev, dtype=torch.float32)
-    L.cdf_unpack_reduce(P(ws), P(dMb), ns, B, HD, dim, ldw, HD * ldw, ldw, 1, 0, 1, S)
-    if b_out is not None:
-        L.cdf_unpack_reduce(P(bsum), P(grad_of(b_out)), B * ns, 1, 1, dim, ldw, 0, 0, 1, 1, 1, S)
+    _bgemm(S, P(dy), lddy, P(Mb), ldw, P(dqkv), lddq, n, dim, HD, b_trans=1, batch=B, a_bs=n * lddy, w_bs=HD * ldw, y_bs=n * lddq)
+    dMb = _image_wgrad(qkv, HD, dy, dim, ldw, b_out, S)       # dM_b = q[b]^T dy[b]
     return _linattn_out_bwd(dMb, ctx, ctxs, w_out, heads, scale)
 
 
@@ -716,8 +759,8 @@ def _linattn_out_bwd(dMb, ctx, ctxs, w_out, heads, scale):
     # d(ctxs)[b,h][d][e] = sum_c dM_b[h*32 + d][c] W_out[c][h*32 + e]; dctx = scale * that; rvec = rowwise <dctx, ctx>
     wp = packed(w_out, "conv_fwd")
     raw = torch.empty((B, heads, 32, 32), device=dev, dtype=torch.float32)
-    L.cdf_conv_gemm(P(dMb), ldw, P(wp), ldw, P(raw), 32, 1, 1, 32, dim, 1, 32, 32, 1, 32, 1, 1, 1, _one_tap(32).desc,
-                    0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, B, HD * ldw, 0, heads * 1024, heads, 32 * ldw, 32 * ldw, 1024, S)
+    _bgemm(S, P(dMb), ldw, P(wp), ldw, P(raw), 32, 32, dim, 32, b_trans=1, batch=B, a_bs=HD * ldw, y_bs=heads * 1024,
+           batch2=heads, a_bs2=32 * ldw, w_bs2=32 * ldw, y_bs2=1024)
     dctx = torch.empty_like(raw)
     rvec = torch.empty((B, HD), device=dev, dtype=torch.float32)
     L.cdf_linattn_dctx_finish(P(raw), P(ctx), P(dctx), P(rvec), B * heads * 32, scale, S)
@@ -727,7 +770,7 @@ def _linattn_out_bwd(dMb, ctx, ctxs, w_out, heads, scale):
         hp = _HEADSPLIT[heads] = _headsplit_plan(heads)
     nsw = max(1, min(16, (B * 32) // 64))                      # B * 32 contraction rows: a few blocks each instead of one long serial loop
     wsw = torch.empty((nsw, heads, 32, ldw), device=dev, dtype=torch.float32)
-    L.cdf_conv_wgrad(P(ctxs), 32, P(dMb), ldw, P(wsw), ldw, B, 1, 32, heads, 32, 1, heads, 32, 1, 32, dim, heads, hp.desc, nsw, 1, 0, 0, 0, 0, S)
+    _bwgrad(S, hp, ctxs, 32, dMb, ldw, wsw, ldw, B, 32, dim, nsw)
     L.cdf_unpack_reduce(P(wsw), P(grad_of(w_out)), nsw, heads, 32, dim, ldw, 32, 1, HD, 1, 1, S)
     return dctx, rvec
 
@@ -739,32 +782,22 @@ def _linattn_out_bwd(dMb, ctx, ctxs, w_out, heads, scale):
 # written, re-read by the context pass, the data gradient and the weight gradient), the batched GEMMs stream xn / dy (dim channels)
 # instead of q / dq (128), and Wq's gradient is dWq = sum_b M_b . dN_b^T with dN_b = xn_b^T dy_b.
 def linattn_fold(xn, ctxs, w_qkv, w_out, b_out, res, heads, y=None):
-    """y = xn . N_b + b_out + res.  Returns (y, Mb, Nb)."""
-    L, S = rt.lib(), rt.stream(xn)
+    """y = xn . N_b + b_out + res.  Returns (y, Mb, Nb).  A bf16 `res` (bf16 activation storage) is read from the bf16 stream and the
+    result enters it rounded once -- no fp32 copy of either."""
+    S = rt.stream(xn)
     B, H, W, _ = xn.shape
     n, HD, dim = H * W, heads * 32, w_out.shape[0]
-    wp = packed(w_out, "conv_fwd")                            # [1][HD][r4(dim)]
-    ldw = wp.shape[-1]
-    Mb = torch.empty((B, HD, ldw), device=xn.device, dtype=torch.float32)
-    L.cdf_conv_gemm(P(ctxs), 32, P(wp), ldw, P(Mb), ldw, 1, 1, 32, 32, 1, 32, dim, 1, 32, 1, 1, 1, _one_tap(32).desc,
-                    0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, B, heads * 1024, 0, HD * ldw, heads, 1024, 32 * ldw, 32 * ldw, S)
+    Mb = _out_matrix(ctxs, w_out, S)
+    ldw = Mb.shape[-1]
     wq = packed(w_qkv, "conv_fwd")                            # [1][dim][r4(3 HD)]: row i, columns 0 .. HD-1 = Wq[:, i]
     Nb = torch.empty((B, dim, ldw), device=xn.device, dtype=torch.float32)
-    L.cdf_conv_gemm(P(wq), wq.shape[-1], P(Mb), ldw, P(Nb), ldw, 1, 1, dim, HD, 1, dim, dim, 1, dim, 1, 1, 1, _one_tap(dim).desc,
-                    0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, B, 0, HD * ldw, dim * ldw, 1, 0, 0, 0, S)
-    if is_bf(res):
-        # bf16 activation storage: the residual is read from the bf16 stream and the result enters it rounded once -- no fp32 copy of either
-        if y is None:
-            y = new_bf(xn, B, H, W, dim)
-        ldx, ldy = ld_of(xn), ld_of(y)
-        L.cdf_conv_gemm_io(P(xn), ldx, P(Nb), ldw, 0, ldy, 1, 1, n, dim, 1, n, dim, 1, n, 1, 1, 1, _one_tap(n).desc,
-                           P(b_out), 0, 0, P(res), ld_of(res), 0, 0, 0, 0, 0, 0, 0, 0, B, n * ldx, dim * ldw, n * ldy, 1, 0, 0, 0, IO_RES, P(y), ldy, S)
-        return y, Mb, Nb
+    _bgemm(S, P(wq), wq.shape[-1], P(Mb), ldw, P(Nb), ldw, dim, HD, dim, batch=B, w_bs=HD * ldw, y_bs=dim * ldw)
+    bf = is_bf(res)
     if y is None:
-        y = new_feat(xn, B, H, W, dim)
+        y = new_bf(xn, B, H, W, dim) if bf else new_feat(xn, B, H, W, dim)
     ldx, ldy = ld_of(xn), ld_of(y)
-    L.cdf_conv_gemm(P(xn), ldx, P(Nb), ldw, P(y), ldy, 1, 1, n, dim, 1, n, dim, 1, n, 1, 1, 1, _one_tap(n).desc,
-                    P(b_out), 0, 0, P(res), 0 if res is None else ld_of(res), 0, 0, 0, 0, 0, 0, 0, 0, B, n * ldx, dim * ldw, n * ldy, 1, 0, 0, 0, S)
+    _bgemm(S, P(xn), ldx, P(Nb), ldw, 0 if bf else P(y), ldy, n, dim, dim, bias=b_out, res=res, batch=B, a_bs=n * ldx, w_bs=dim * ldw,
+           y_bs=n * ldy, io=IO_RES if bf else 0, y_bf=P(y) if bf else 0, ld_ys=ldy if bf else 0)
     return y, Mb, Nb
 
 
@@ -786,10 +819,7 @@ def linattn_kvctx(xn, dim, w_qkv, heads, scale):
     P_ = L.cdf_linattn_kvctx_parts(B, n, rt.KVCTX_SLOTS)
     ws = torch.empty((B * P_ * (2 * HD + heads * 1024),), device=dev, dtype=torch.float32)
     L.cdf_linattn_kvctx(P(xn), ld_of(xn), P(wp[0]), P(wp[1]), wp[0].shape[-1], P(kv), 2 * HD, P(ws), B, n, dim, heads, rt.KVCTX_SLOTS, S)
-    ctx = torch.empty((B, heads, 32, 32), device=dev, dtype=torch.float32)
-    ctxs = torch.empty_like(ctx)
-    kmax = torch.empty((B, HD), device=dev, dtype=torch.float32)
-    ksum = torch.empty((B, HD), device=dev, dtype=torch.float32)
+    ctx, ctxs, kmax, ksum = _context_buffers(dev, B, heads)
     L.cdf_linattn_finalize(P(ws), P_, P(ctx), P(ctxs), P(kmax), P(ksum), B, heads, scale, S)
     return kv, ctx, ctxs, kmax, ksum
 
@@ -800,31 +830,16 @@ def linattn_fold_bwd(xn, dy, Mb, Nb, ctx, ctxs, w_qkv, w_out, b_out, heads, scal
     L, S = rt.lib(), rt.stream(xn)
     B, H, W, _ = xn.shape
     n, HD, dim = H * W, heads * 32, w_out.shape[0]
-    ldw, ldx, lddy = Mb.shape[-1], ld_of(xn), ld_of(dy)
-    dev = xn.device
+    ldw, lddy, dev = Mb.shape[-1], ld_of(dy), xn.device
     dxn = new_feat(xn, B, H, W, dim)
-    L.cdf_conv_gemm(P(dy), lddy, P(Nb), ldw, P(dxn), ld_of(dxn), 1, 1, n, dim, 1, n, dim, 1, n, 1, 1, 1, _one_tap(n).desc,
-                    0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, B, n * lddy, dim * ldw, n * ld_of(dxn), 1, 0, 0, 0, S)
-    # dN_b = xn[b]^T dy[b] (split-K slabs [split][b], summed in one pass); the bias gradient = column sums of dy as it streams by
-    wplan = cd.conv_wgrad(1, n, 1, 1, 1, 0, 0, 0, 0)
-    t1 = 1 if dim <= 64 else (dim + 127) // 128
-    ns = best_nsplit(t1 * t1 * B, 1024, max(1, n // 256))
-    ws = torch.empty((ns, B, dim, ldw), device=dev, dtype=torch.float32)
-    bsum = torch.empty((B * ns, ldw), device=dev, dtype=torch.float32) if b_out is not None else None
-    L.cdf_conv_wgrad(P(xn), ldx, P(dy), lddy, P(ws), ldw, 1, 1, n, 1, n, 1, 1, n, 1, dim, dim, 1, wplan.desc, ns, B, n * ldx, n * lddy, -1, P(bsum), S)
-    dNb = torch.empty((B, dim, ldw), device=dev, dtype=torch.float32)
-    L.cdf_unpack_reduce(P(ws), P(dNb), ns, B, dim, dim, ldw, dim * ldw, ldw, 1, 0, 1, S)
-    if b_out is not None:
-        L.cdf_unpack_reduce(P(bsum), P(grad_of(b_out)), B * ns, 1, 1, dim, ldw, 0, 0, 1, 1, 1, S)
+    _bgemm(S, P(dy), lddy, P(Nb), ldw, P(dxn), ld_of(dxn), n, dim, dim, b_trans=1, batch=B, a_bs=n * lddy, w_bs=dim * ldw, y_bs=n * ld_of(dxn))
+    dNb = _image_wgrad(xn, dim, dy, dim, ldw, b_out, S)       # dN_b = xn[b]^T dy[b]
     # dM_b = Wq . dN_b  (Wq = rows 0 .. HD-1 of the to_qkv weight, a plain [HD][dim] matrix in place)
-    wq_rows = w_qkv.detach()
     dMb = torch.empty((B, HD, ldw), device=dev, dtype=torch.float32)
-    L.cdf_conv_gemm(P(wq_rows), dim, P(dNb), ldw, P(dMb), ldw, 1, 1, HD, dim, 1, HD, dim, 1, HD, 1, 1, 1, _one_tap(HD).desc,
-                    0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, B, 0, dim * ldw, HD * ldw, 1, 0, 0, 0, S)
+    _bgemm(S, P(w_qkv.detach()), dim, P(dNb), ldw, P(dMb), ldw, HD, dim, dim, batch=B, w_bs=dim * ldw, y_bs=HD * ldw)
     # dWq[hd][i] += sum_b sum_c M_b[hd][c] dN_b[i][c]
     T = torch.empty((B, HD, ldw), device=dev, dtype=torch.float32)
-    L.cdf_conv_gemm(P(Mb), ldw, P(dNb), ldw, P(T), ldw, 1, 1, HD, dim, 1, HD, dim, 1, HD, 1, 1, 1, _one_tap(HD).desc,
-                    0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, B, HD * ldw, dim * ldw, HD * ldw, 1, 0, 0, 0, S)
+    _bgemm(S, P(Mb), ldw, P(dNb), ldw, P(T), ldw, HD, dim, dim, b_trans=1, batch=B, a_bs=HD * ldw, w_bs=dim * ldw, y_bs=HD * ldw)
     L.cdf_unpack_reduce(P(T), P(grad_of(w_qkv)), B, 1, HD, dim, ldw, 0, dim, 1, 1, 1, S)
     dctx, rvec = _linattn_out_bwd(dMb, ctx, ctxs, w_out, heads, scale)
     return dxn, dctx, rvec
@@ -857,23 +872,6 @@ def linattn_bwd_core(qkv, dctx, rvec, kmax, ksum, dqkv, heads, koff=None, planes
     _head_gemm(pn, 0, dctx, dqkv, 2 * HD, B, n, heads, False)      # dv[n,e] = sum_d P[n,d] dctx[d,e]
     L.cdf_linattn_dk(P(pn), HD, P(dp), HD, P(rvec), P(dqkv) + 4 * HD, 3 * HD, B, n, heads, S)
     return dqkv
-
-
-def linattn_context(qkv, heads, scale, koff=None):
-    """(ctx, ctxs = scale * ctx, kmax, ksum) of LinearAttention (no output product).  koff: channel offset of k in qkv's rows
-    (default heads*32: the (q|k|v) tensor; 0 for a (k|v) tensor)."""
-    L = rt.lib()
-    B, H, W, _ = qkv.shape
-    n, HD = H * W, heads * 32
-    koff = HD if koff is None else koff
-    dev = qkv.device
-    ctx = torch.empty((B, heads, 32, 32), device=dev, dtype=torch.float32)
-    ctxs = torch.empty_like(ctx)
-    kmax = torch.empty((B, HD), device=dev, dtype=torch.float32)
-    ksum = torch.empty((B, HD), device=dev, dtype=torch.float32)
-    ws = torch.empty((L.cdf_linattn_ws_floats(B, n, heads),), device=dev, dtype=torch.float32)
-    L.cdf_linattn_context(P(qkv), ld_of(qkv), koff, P(ctx), P(ctxs), P(kmax), P(ksum), P(ws), B, n, heads, scale, 1, rt.stream(qkv))
-    return ctx, ctxs, kmax, ksum
 
 
 def nchw_to_nhwc(x):
@@ -930,21 +928,13 @@ def groupnorm_bwd(dy, x, gamma_p, beta_p, mean, rstd, groups, silu, dx=None, dro
     return dx
 
 
-_ONE_TAP = None
-
-
-def _one_tap(n):
-    return cd.conv_fwd(1, n, 1, 1, 1, 0, 0, 0, 0)
-
-
 def bgemm_nt(a, b):
     """[nb, n, K] x [nb, m, K]^T -> [nb, n, r4(m)] (valid columns :m)."""
     nb, n, K = a.shape
     m = b.shape[1]
     out = new_feat(a, nb, 1, n, m).view(nb, n, r4(m))
-    plan = _one_tap(n)
-    rt.lib().cdf_conv_gemm(P(a), a.stride(1), P(b), b.stride(1), P(out), r4(m), 1, 1, n, K, 1, n, m, 1, n, 1, 1, 1, plan.desc,
-                           0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, nb, a.stride(0), b.stride(0), n * r4(m), 1, 0, 0, 0, rt.stream(a))
+    _bgemm(rt.stream(a), P(a), a.stride(1), P(b), b.stride(1), P(out), r4(m), n, K, m, b_trans=1, batch=nb, a_bs=a.stride(0), w_bs=b.stride(0),
+           y_bs=n * r4(m))
     return out
 
 
@@ -954,9 +944,7 @@ def bgemm_nn(a, b, K=None):
     K = a.shape[2] if K is None else K
     m = b.shape[2]
     out = new_feat(a, nb, 1, n, m).view(nb, n, r4(m))
-    plan = _one_tap(n)
-    rt.lib().cdf_conv_gemm(P(a), a.stride(1), P(b), b.stride(1), P(out), r4(m), 1, 1, n, K, 1, n, m, 1, n, 1, 1, 1, plan.desc,
-                           0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, nb, a.stride(0), b.stride(0), n * r4(m), 1, 0, 0, 0, rt.stream(a))
+    _bgemm(rt.stream(a), P(a), a.stride(1), P(b), b.stride(1), P(out), r4(m), n, K, m, batch=nb, a_bs=a.stride(0), w_bs=b.stride(0), y_bs=n * r4(m))
     return out
 
 
@@ -966,9 +954,8 @@ def bgemm_tn(a, b, CA=None):
     CA = a.shape[2] if CA is None else CA
     m = b.shape[2]
     out = torch.empty((nb, CA, r4(m)), device=a.device, dtype=torch.float32)
-    tap = cd.conv_wgrad(1, K, 1, 1, 1, 0, 0, 0, 0)
-    rt.lib().cdf_conv_wgrad(P(a), a.stride(1), P(b), b.stride(1), P(out), r4(m), 1, 1, K, 1, K, 1, 1, K, 1, CA, m, 1, tap.desc, 1, nb,
-                            a.stride(0), b.stride(0), CA * r4(m), 0, rt.stream(a))
+    _bwgrad(rt.stream(a), cd.conv_wgrad(1, K, 1, 1, 1, 0, 0, 0, 0), a, a.stride(1), b, b.stride(1), out, r4(m), 1, CA, m, 1, batch=nb,
+            a_bs=a.stride(0), b_bs=b.stride(0), o_bs=CA * r4(m))
     return out
 
 
@@ -1062,19 +1049,8 @@ def conv_gemm_bf(plan, x, Cin, wp, Cout, y=None, bias=None, sbias=None, res=None
     B = x.shape[0]
     if y is None:
         y = new_bf(x, B, plan.OH, plan.OW, Cout)             # (asserts Cout % 8: a bf16 tensor must be a legal operand plane of the next GEMM)
-    ldv = lambda t: 0 if t is None else ld_of(t)
-    M = B * plan.QH * plan.QW
-    ws, nws = None, 0
-    if M <= 4096 and x.device.type != "meta":
-        ks = rt.lib().cdf_conv_gemm_bf16x_ksplit(M, Cout, plan.nphase, plan.desc[2], rt.tune_ptr())
-        if ks > 1:
-            nws = ks * M * r4(Cout)
-            ws = torch.empty((nws,), device=x.device, dtype=torch.float32)
     io = (IO_RES if is_bf(res) else 0) | (IO_PRE if is_bf(pre) else 0) | (IO_MUL if is_bf(mul) else 0) | (IO_PRE_GRAD if pre_grad else 0)
-    rt.lib().cdf_conv_gemm_bf16x_io(P(x), 0, ld_of(x), P(zero_page(x.device)), P(wp[0]), 0, wp[0].shape[-1], 0, Cout,
-                                    B, plan.H, plan.W, Cin, plan.OH, plan.OW, Cout, plan.QH, plan.QW, plan.os, plan.istride, plan.nphase,
-                                    plan.desc, P(bias), P(sbias), 0 if sbias is None else sbias.stride(0), P(res), ldv(res), P(pre),
-                                    ldv(pre), P(mul), ldv(mul), act, mul_mode, 0, io, P(y), 0, ld_of(y), P(ws), nws, rt.tune_ptr(), rt.stream(x))
+    _gemm_bf16x(plan, x, None, ld_of(x), wp, Cin, Cout, None, Cout, (y, None), ld_of(y), bias, sbias, res, pre, mul, act, mul_mode, 0, io)
     return y
 
 

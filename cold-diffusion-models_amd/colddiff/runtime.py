@@ -42,7 +42,9 @@ import contextlib as _contextlib
 
 @_contextlib.contextmanager
 def precision_scope(p):
-    """Run a region in another arithmetic mode (the packed-weight cache is keyed by the mode, so nothing is invalidated)."""
+    """Run a region in another arithmetic mode.  The packed-weight cache keeps ONE layout per (parameter, kind) and remembers the mode it
+    was packed in: the first use of a weight in the other mode packs it again over that slot (every kind, not only the bf16 planes whose
+    contents depend on the mode), and so does the first use after the region ends."""
     global precision
     assert p in ("f32", "bf16x3", "bf16"), p
     saved, precision = precision, p
