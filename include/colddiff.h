@@ -28,7 +28,7 @@ extern "C" {
 /* Bumped whenever an exported signature changes incompatibly (rounds 1-3 all answered 1 while arguments were added: `tiled`,
  * `onepass`, `slots`, `tune`).  cdf_abi_version() returns the value the LIBRARY was built with; a binding compares it with the
  * header it was generated from before the first call (colddiff/_lib.py does) -- a mismatched pair would read shifted arguments. */
-#define CDF_ABI_VERSION 6
+#define CDF_ABI_VERSION 7
 
 #define CDF_E_INVALID (-1)
 #define CDF_E_UNSUPPORTED (-2)
@@ -95,6 +95,33 @@ int cdf_blend_qsample(const float* x1, const float* x2, const float* alphas, con
                       int B, int C, long long HW, void* stream);
 int cdf_blend_step(const float* img, const float* x1, const float* x2, const float* alphas, const float* one_minus, int t, float* out,
                    long long HW, long long n, void* stream);
+
+/* ---- colour forward process (decolor-diffusion/diffusion/forward_process_impl.py:131-218, diffusion.py:196-245, 344-388) --------------
+ * DeColorization: up to T per-pixel 3 x 3 colour mixes (nn.Conv2d(3, 3, 1) upstream), optionally each wrapped in Lab <-> RGB conversions.
+ * x / y / total / snap / img: NCHW fp32 [B,3,H,W], HW = H * W.  w: [T][3][3] fp32 in device memory, row = output channel; one step is
+ *   y_c = (w[c][0] * x_0 + w[c][1] * x_1) + w[c][2] * x_2        (plain fp32 multiplies and adds in that order, no contraction)
+ * Row b runs n_b steps 0 .. n_b-1 with its pixel's three channels in registers: n_b = nsteps_b[b] (int64 per sample, device memory) or, with
+ * nsteps_b == NULL, the scalar nsteps.  A NEGATIVE n_b marks a row that is passed through untouched into every output (the t == -1 rows
+ * of the Step / Step_Gradient train routines).  0 <= n_b <= T, 0 <= nmax <= T.
+ *   y     : state after n_b steps; with img != NULL instead y = (img - x_{n_b}) + snap            (Algorithm 2, in that association)
+ *   total : optional, state of the row after nmax steps (q_sample(return_total_blur=True))
+ *   snap  : optional, state after min(n_b, nmax - 1) steps (0 when nmax == 0) -- what sample_one_step's `x_times_sub_1`, re-cloned from
+ *           the whole batch at the top of every iteration, ends up holding for a row (diffusion.py:221-237)
+ *   lab   : != 0: each step is rgb2lab(mix(lab2rgb(x))) per pixel, lab2rgb's clamp to [0, 1] included
+ * One block works on pixels of one image (n_b and the weights are block-uniform; the row's weight slice is staged in LDS once);
+ * every input plane is read once and every output written once whatever n_b is.  T <= 1024.  y may alias x. */
+int cdf_color_chain(const float* x, float* y, float* total, float* snap, const float* img, const float* w, const int64_t* nsteps_b,
+                    int B, int C, long long HW, int T, int nsteps, int nmax, int lab, void* stream);
+/* Stand-alone conversions in the reference's (-1, 1) RGB convention (decolor-diffusion/diffusion/utils.py:113-222; the sRGB <-> linear
+ * and RGB <-> XYZ parts restated from kornia's published formulae): to_rgb == 0: y = rgb2lab(x), else y = lab2rgb(x) (clamped).
+ * The same device functions as the chain kernel.  y may alias x. */
+int cdf_lab_convert(const float* x, float* y, int B, int C, long long HW, int to_rgb, void* stream);
+/* UnetConvNextBlock(output_mean_scale=True) (model/unet_convnext.py:198, 222-224): out = (y - mean_b(x)) + mean_b(y), per-image means over
+ * the n = C*H*W elements of image b, as a two-stage block reduction (fixed order: deterministic).  Backward with respect to y:
+ * dx = dy + mean_b(dy) (x is the network input and takes no gradient).  ws >= B * cdf_mean_shift_nchunk(n) * 2 floats. */
+int cdf_mean_shift_nchunk(long long n);
+int cdf_mean_shift(const float* x, const float* y, float* out, float* ws, int B, long long n, void* stream);
+int cdf_mean_shift_bwd(const float* dy, float* dx, float* ws, int B, long long n, void* stream);
 
 /* L1 / L2 training loss (deblurring_diffusion_pytorch.py:966-971): out[0] = mean|x-y| or
  * mean (x-y)^2; backward writes d loss / d y scaled by gout[0]. partial: >= 1024 floats. */
