@@ -207,15 +207,29 @@ class DecolorDiffusion(TwoPhase, nn.Module):
         self.single_snow = single_snow
         self.to_lab = to_lab
         self.recon_noise_std = recon_noise_std
+        self.forward_process = self._build_forward_process(
+            forward_process_type, decolor_routine=decolor_routine, decolor_ema_factor=decolor_ema_factor,
+            decolor_total_remove=decolor_total_remove, load_snow_base=load_snow_base, load_path=load_path, fix_brightness=fix_brightness,
+            results_folder=results_folder)
+
+    # -- the two hooks a package with another forward process overrides (colddiff/snow.py) ---------------
+    def _build_forward_process(self, forward_process_type, *, decolor_routine, decolor_ema_factor, decolor_total_remove, **snow_kw):
         if forward_process_type == 'Decolorization':
-            self.forward_process = DeColorization(decolor_routine=decolor_routine, decolor_ema_factor=decolor_ema_factor,
-                                                  decolor_total_remove=decolor_total_remove, channels=self.channels,
-                                                  num_timesteps=self.num_timesteps, to_lab=self.to_lab)
+            return DeColorization(decolor_routine=decolor_routine, decolor_ema_factor=decolor_ema_factor,
+                                  decolor_total_remove=decolor_total_remove, channels=self.channels,
+                                  num_timesteps=self.num_timesteps, to_lab=self.to_lab)
         elif forward_process_type == 'Snow':
             raise NotImplementedError("forward_process_type='Snow' is not built (the snowification forward process needs host-side snow "
                                       "layers; this package implements forward_process_type='Decolorization')")
         else:
             raise NotImplementedError(f"forward_process_type={forward_process_type!r}: 'Decolorization' is the forward process of this package")
+
+    def _chain(self, og, start=None, **kw):
+        """The state of every row after its step count, in ONE launch (`color_chain`'s keywords).  `og`: the images the process degrades;
+        `start`: what a row that takes zero steps holds, when that is not `og` (the noised prediction of `x0_step_down`) -- the colour
+        chain, a composition of steps, simply starts there."""
+        x = D._img(og if start is None else start)
+        return color_chain(x, self._table(x.device), lab=self.to_lab, **kw)
 
     # -- helpers --------------------------------------------------------------------------------------
     def _hw(self):
@@ -238,7 +252,7 @@ class DecolorDiffusion(TwoPhase, nn.Module):
     def _q_sample_nonneg(self, x_start, t):
         """q_sample for t >= 0 everywhere (what forward() draws): n_b = t_b + 1 computed on the device, nothing synchronises."""
         x_start = rt.check(x_start)
-        return color_chain(x_start, self._table(x_start.device), nsteps_b=t + 1, lab=self.to_lab)
+        return self._chain(x_start, nsteps_b=t + 1)
 
     # -- sampling -------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -252,19 +266,18 @@ class DecolorDiffusion(TwoPhase, nn.Module):
         if self.recon_noise_std > 0.0:
             self.recon_noise_std_array = torch.linspace(0.0, self.recon_noise_std, steps=self.num_timesteps)
         if self.train_routine in _FINAL_ROUTINES:
-            table = self._table(img.device)
             t = D._steps(t, img.shape[0])
             if self.sampling_routine == 'default':
                 # rows advance while cur_time < t - 1, for i in range(t.max() - 1): n_b = max(t_b - 1, 0) steps
-                x = color_chain(x, table, nsteps_b=(t - 1).clamp(min=0), lab=self.to_lab)
+                x = self._chain(x, nsteps_b=(t - 1).clamp(min=0))
             elif self.sampling_routine == 'x0_step_down':
-                x_times = x
+                x_times = None
                 if self.recon_noise_std > 0.0:
                     x_times = x + torch.normal(0.0, self.recon_noise_std, size=x.size(), device=x.device)
                 # x_times: t_b steps; x_times_sub_1 is re-cloned from the WHOLE batch at the top of every global iteration, so a row holds
                 # its state after min(t_b, t.max() - 1) steps (and x_times itself when t.max() == 0): the kernel's `snap`
                 tmax = int(t.max()) if _tmax is None else int(_tmax)          # (upstream's `range(t.max())`; the samplers pass it)
-                x = color_chain(x_times, table, nsteps_b=t, nmax=tmax, img=img, lab=self.to_lab)
+                x = self._chain(x, start=x_times, nsteps_b=t, nmax=tmax, img=img)
         elif self.train_routine == 'Step':
             img = x
         elif self.train_routine == 'Step_Gradient':
@@ -289,7 +302,7 @@ class DecolorDiffusion(TwoPhase, nn.Module):
             t = self.num_timesteps
         img = rt.check(img)
         # the t forward steps of diffusion.py:270-273 as one launch
-        img = color_chain(img, self._table(img.device), nsteps=t, lab=self.to_lab) if t > 0 else img.clone()
+        img = self._chain(img, nsteps=t) if t > 0 else img.clone()
         init_pred = None
         xt = img
         direct_recons = None
@@ -341,14 +354,13 @@ class DecolorDiffusion(TwoPhase, nn.Module):
         picked = t[pos]                                          # ... and the step upstream reads for it: t at THAT index
         mx = t.max()
         nb = torch.where(keep, torch.where(picked < 0, mx, picked) + 1, torch.full_like(t, -1))
-        table = self._table(x_start.device)
         if return_total_blur:
             # the total blur is the state after max(t) + 1 steps: ONE scalar read, as upstream's `range(max_iters + 1)`
             max_iters = int(mx)
             if max_iters < 0:
                 return x_start.clone()                           # (every row is t == -1: upstream returns the single tensor)
-            return color_chain(x_start, table, nsteps_b=nb, nmax=max_iters + 1, want_total=True, lab=self.to_lab)
-        return color_chain(x_start, table, nsteps_b=nb, lab=self.to_lab)   # nothing synchronises; all rows -1: every row passes through
+            return self._chain(x_start, nsteps_b=nb, nmax=max_iters + 1, want_total=True)
+        return self._chain(x_start, nsteps_b=nb)   # nothing synchronises; all rows -1: every row passes through
 
     def loss_func(self, pred, true):
         if self.loss_type == 'l1':
@@ -407,10 +419,9 @@ class DecolorDiffusion(TwoPhase, nn.Module):
         if t == None:                                          # noqa: E711
             t = self.num_timesteps
         img = rt.check(img)
-        table = self._table(img.device)
         Forward = [img]
         for i in range(t):
-            n_img = color_chain(img, table, nsteps=i + 1, lab=self.to_lab)       # q_sample(img, full(i))
+            n_img = self._chain(img, nsteps=i + 1)       # q_sample(img, full(i))
             Forward.append(n_img)
         Backward = []
         img = n_img
@@ -420,7 +431,7 @@ class DecolorDiffusion(TwoPhase, nn.Module):
             Backward.append(img)
             # img - q_sample(x1_bar, t - 1) + q_sample(x1_bar, t - 2): t steps, the state one step earlier, and the combine, in one launch
             # (t - 1 == 0: xt_sub1_bar = x1_bar itself = the state after 0 steps)
-            img = color_chain(x1_bar, table, nsteps=t, nmax=t, img=img, lab=self.to_lab)
+            img = self._chain(x1_bar, nsteps=t, nmax=t, img=img)
             t = t - 1
         return Forward, Backward, img
 

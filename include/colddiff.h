@@ -28,7 +28,7 @@ extern "C" {
 /* Bumped whenever an exported signature changes incompatibly (rounds 1-3 all answered 1 while arguments were added: `tiled`,
  * `onepass`, `slots`, `tune`).  cdf_abi_version() returns the value the LIBRARY was built with; a binding compares it with the
  * header it was generated from before the first call (colddiff/_lib.py does) -- a mismatched pair would read shifted arguments. */
-#define CDF_ABI_VERSION 7
+#define CDF_ABI_VERSION 8
 
 #define CDF_E_INVALID (-1)
 #define CDF_E_UNSUPPORTED (-2)
@@ -122,6 +122,34 @@ int cdf_lab_convert(const float* x, float* y, int B, int C, long long HW, int to
 int cdf_mean_shift_nchunk(long long n);
 int cdf_mean_shift(const float* x, const float* y, float* out, float* ws, int B, long long n, void* stream);
 int cdf_mean_shift_bwd(const float* dy, float* dx, float* ws, int B, long long n, void* stream);
+
+/* ---- snow forward process (snowification/diffusion/forward_process_impl.py:220-372, diffusion.py:196-245, 344-388) ---------------------
+ * Snow.forward(x, i, og=) never reads x: the state after any number of steps is a pointwise function of the original image og and the
+ * index i of the last step.  With og_r = (og + 1) / 2, per pixel p and channel c (plain fp32 in this order, no contraction):
+ *   gray   = ((0.299 r + 0.587 g) + 0.114 b) * 1.5 + 0.5
+ *   scaled = br[i] * og_r + omb[i] * max(og_r, gray)               (og_r itself when fix_brightness != 0)
+ *   D(og, i) = clip((scaled + snow[i][l][p]) + snow[i][l][HW - 1 - p], 0, 1) * 2 - 1
+ *
+ * cdf_snow_layers builds the planes snow[T][L][H][W] (ONE channel: the reference's three are identical) from the host-made base
+ * [L][H*W]: per step t the base is zeroed below thres[t], clipped to [0, 1] -- both applied as each source pixel is read -- and
+ * blurred by the k taps[t] along x (vertical[t * L + l] == 0; source (y, x + j - k/2), weight taps[t][j]) or along y (!= 0; source
+ * (y + j - k/2, x), weight taps[t][k - 1 - j]), sources outside the image contributing 0, j ascending in fp32.  k odd, <= 63. */
+int cdf_snow_layers(const float* base, const float* thres, const float* taps, const unsigned char* vertical, float* snow, int H, int W,
+                    int L, int T, int k, void* stream);
+/* The step-count convention of cdf_color_chain: row b has the count n_b = nsteps_b[b] (int64, device memory) or the scalar nsteps; its
+ * state after n steps is D(og_b, n - 1) for n >= 1, start_b for n == 0 (start == NULL: og_b), and for a NEGATIVE count the row of og,
+ * passed through into every output.  n_b <= T, 0 <= nmax <= T.
+ *   y     : state after n_b steps; with img != NULL instead y = (img - state) + snap-state          (Algorithm 2, in that association)
+ *   total : optional, state after nmax steps
+ *   snap  : optional, state after min(n_b, nmax - 1) steps (0 when nmax == 0)
+ * Row b reads layer layer_b[b] (int64, device memory; clamped to 0 .. L-1), else b when L > 1 (then B <= L), else 0.  og / start / y /
+ * total / snap / img: NCHW fp32 [B,3,H,W], HW = H * W; br / omb: [T] fp32, float32(br_coef) and float32(1.0 - br_coef).  One lane
+ * handles the three channels of four consecutive pixels with 16-byte accesses (the mirrored plane read is the aligned group at
+ * HW - 4 - p, reversed in registers) when HW % 4 == 0 and every pointer is 16-byte aligned, of one pixel otherwise.  Outputs must not
+ * alias the snow planes; y may alias og. */
+int cdf_snow_chain(const float* og, const float* start, float* y, float* total, float* snap, const float* img, const float* snow,
+                   const float* br, const float* omb, const int64_t* nsteps_b, const int64_t* layer_b, int B, long long HW, int L, int T,
+                   int nsteps, int nmax, int fix_brightness, void* stream);
 
 /* L1 / L2 training loss (deblurring_diffusion_pytorch.py:966-971): out[0] = mean|x-y| or
  * mean (x-y)^2; backward writes d loss / d y scaled by gout[0]. partial: >= 1024 floats. */
