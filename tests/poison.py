@@ -59,3 +59,27 @@ def nan_empty(be, *shape, dtype=torch.float32):
     Use it for every buffer a kernel's contract says it overwrites; buffers whose pad columns the product guarantees to be
     zero (new_feat(zero=True) when C % 4) stay torch.zeros."""
     return poison_(torch.empty(*shape, device=be.device, dtype=dtype))
+
+
+GUARD = 4096          # floats on either side of every output
+
+
+class Guarded:
+    """n output tensors of one shape carved out of a single poisoned buffer, GUARD floats apart."""
+
+    def __init__(self, dev, shape, n):
+        self.numel = 1
+        for s in shape:
+            self.numel *= s
+        self.stride = self.numel + GUARD
+        self.buf = torch.empty(GUARD + n * self.stride, device=dev, dtype=torch.float32)
+        self.outs = [self.buf[GUARD + i * self.stride: GUARD + i * self.stride + self.numel].view(shape) for i in range(n)]
+        self.mask = torch.ones(self.buf.numel(), dtype=torch.bool, device=dev)
+        for i in range(n):
+            self.mask[GUARD + i * self.stride: GUARD + i * self.stride + self.numel] = False
+
+    def poison(self):
+        poison_(self.buf)
+
+    def guards_intact(self):
+        return bool(torch.isnan(self.buf[self.mask]).all())

@@ -8,12 +8,11 @@ import torch
 
 import decolor_ref as R
 from emu_util import P
-from poison import poison_
+from poison import GUARD, Guarded  # noqa: F401  (GUARD: the module kept the name)
 from test_color_kernels import LAB_CHAIN_TOL, LAB_SCALE, RGB_CHAIN_TOL
 from test_kernels_production import bits_equal, sample
 
 pytestmark = pytest.mark.gpu
-GUARD = 4096          # floats on either side of every output
 
 
 @pytest.fixture(scope="module")
@@ -22,27 +21,6 @@ def be():
     shapes in test_color_kernels.py)."""
     from conftest import Backend
     return Backend("hip")
-
-
-class Guarded:
-    """n output tensors of one shape carved out of a single poisoned buffer, GUARD floats apart."""
-
-    def __init__(self, dev, shape, n):
-        self.numel = 1
-        for s in shape:
-            self.numel *= s
-        self.stride = self.numel + GUARD
-        self.buf = torch.empty(GUARD + n * self.stride, device=dev, dtype=torch.float32)
-        self.outs = [self.buf[GUARD + i * self.stride: GUARD + i * self.stride + self.numel].view(shape) for i in range(n)]
-        self.mask = torch.ones(self.buf.numel(), dtype=torch.bool, device=dev)
-        for i in range(n):
-            self.mask[GUARD + i * self.stride: GUARD + i * self.stride + self.numel] = False
-
-    def poison(self):
-        poison_(self.buf)
-
-    def guards_intact(self):
-        return bool(torch.isnan(self.buf[self.mask]).all())
 
 
 def _run_twice(g, launch):
