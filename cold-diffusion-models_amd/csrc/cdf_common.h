@@ -37,20 +37,28 @@
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
 typedef float f32x16_t __attribute__((ext_vector_type(16)));
 #endif
-// One-time-PER-DEVICE latch for hipFuncSetAttribute(MaxDynamicSharedMemorySize): a process may drive several devices, and a function
-// attribute belongs to the device that was current when it was set.  Unsynchronised on purpose -- a race only repeats an idempotent call.
-#ifndef CDF_EMU
-struct CdfDeviceLatch {
-    unsigned long long seen = 0;                             // bit d: set on device d (ordinals >= 64 always repeat the call)
-    bool first() {
-        int d = 0;
-        if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= 64) return true;
-        if (seen & (1ull << d)) return false;
-        seen |= 1ull << d;
-        return true;
-    }
-};
+// Launch of a kernel whose dynamic LDS may pass the 64 KB default: hipFuncSetAttribute(MaxDynamicSharedMemorySize) once PER DEVICE and
+// kernel instantiation (a process may drive several devices, and a function attribute belongs to the device that was current when it was
+// set), then the launch.  The latch is unsynchronised on purpose -- a race only repeats an idempotent call.  The simulator has no limit.
+#ifdef CDF_EMU
+#define CDF_LAUNCH_LDS_MAX(max_bytes, kernel, grid, block, shmem, stream, ...) CDF_LAUNCH(kernel, grid, block, shmem, stream, __VA_ARGS__)
+#else
+template <auto Kernel, int MaxBytes>
+static inline void cdf_raise_lds_limit() {
+    static unsigned long long seen = 0;                      // bit d: set on device d (ordinals >= 64 always repeat the call)
+    int d = 0;
+    const bool known = hipGetDevice(&d) == hipSuccess && d >= 0 && d < 64;
+    if (known && (seen & (1ull << d))) return;
+    if (known) seen |= 1ull << d;
+    (void)hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, MaxBytes);
+}
+#define CDF_LAUNCH_LDS_MAX(max_bytes, kernel, grid, block, shmem, stream, ...) \
+    do {                                                                        \
+        cdf_raise_lds_limit<kernel, max_bytes>();                               \
+        CDF_LAUNCH(kernel, grid, block, shmem, stream, __VA_ARGS__);            \
+    } while (0)
 #endif
+#define CDF_LAUNCH_LDS(kernel, grid, block, shmem, stream, ...) CDF_LAUNCH_LDS_MAX(160 * 1024, kernel, grid, block, shmem, stream, __VA_ARGS__)
 // Order the LDS accesses of ONE wave against each other (a wave's LDS operations execute in order on the hardware: only the compiler
 // must not move them; the fiber simulator really has to let the other lanes catch up).
 #ifdef CDF_EMU
@@ -58,6 +66,39 @@ struct CdfDeviceLatch {
 #else
 #define CDF_WAVE_SYNC() __builtin_amdgcn_wave_barrier()
 #endif
+
+// ---- 32 x 32 MFMA accumulators (f32x16_t) ----------------------------------------------------------------
+// Lane l holds column l & 31 of the block; its register r is row cdf_acc_row(r, l >> 5).
+constexpr int cdf_acc_row(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
+__device__ __forceinline__ void cdf_acc_zero(f32x16_t& acc) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+}
+template <int MT, int NT>
+__device__ __forceinline__ void cdf_acc_zero(f32x16_t (&acc)[MT][NT]) {
+#pragma unroll
+    for (int i = 0; i < MT; ++i)
+#pragma unroll
+        for (int j = 0; j < NT; ++j) cdf_acc_zero(acc[i][j]);
+}
+// accumulator -> staging tile (floats, row pitch `pitch`): the 32 x 32 block at rows row0, columns col0; half = lane >> 5, l31 = lane & 31.
+// (A caller that folds the lane's part into `tile` itself passes half = l31 = 0.)
+__device__ __forceinline__ void cdf_acc_stage(float* tile, int pitch, int row0, int col0, const f32x16_t& acc, int half, int l31) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) tile[(row0 + cdf_acc_row(r, half)) * pitch + col0 + l31] = acc[r];
+}
+// ... acc[j]: the block at rows row0, columns col0 + 32 j
+template <int NT>
+__device__ __forceinline__ void cdf_acc_stage(float* tile, int pitch, int row0, int col0, const f32x16_t (&acc)[NT], int half, int l31) {
+#pragma unroll
+    for (int j = 0; j < NT; ++j) cdf_acc_stage(tile, pitch, row0, col0 + j * 32, acc[j], half, l31);
+}
+// ... acc[i][j]: the block at rows row0 + 32 i, columns col0 + 32 j
+template <int MT, int NT>
+__device__ __forceinline__ void cdf_acc_stage(float* tile, int pitch, int row0, int col0, const f32x16_t (&acc)[MT][NT], int half, int l31) {
+#pragma unroll
+    for (int i = 0; i < MT; ++i) cdf_acc_stage(tile, pitch, row0 + i * 32, col0, acc[i], half, l31);
+}
 
 // 256 zero bytes: out-of-range operand elements are loaded from here, so that loads never sit behind a branch.
 // (one copy per translation unit; the contents never change)

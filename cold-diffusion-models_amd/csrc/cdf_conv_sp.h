@@ -5,6 +5,9 @@
 //   k_conv_halo.hip       3 x 3 stride-1 GEMM with the input tile + halo resident in LDS
 //   k_conv_rowhalo.hip    resident row-halo stream kernel (64 / 128 input channels at 128-pixel width)
 //   k_conv_wgrad_spx.hip  pre-split weight gradients (per-tap and row-of-taps kernels), their dispatcher and C entry points
+// Here: the argument structs, the MFMA products (cdf_mma_sp / cdf_mma_tile), the tile epilogue (cdf_sp_epilogue), what the K loops of the three
+// forward kernels share (DMA slot, weight row / offset, DMA segments, fragment reads, the de-phased step) and their LDS layouts (SpxLayout,
+// HaloLayout, RowHaloLayout -- read by the kernel AND its launcher).  Accumulator zeroing / row map / staging and CDF_LAUNCH_LDS: cdf_common.h.
 #pragma once
 #include "cdf_common.h"
 #include "cdf_epilogue.h"
@@ -48,15 +51,7 @@ __device__ __forceinline__ void cdf_sp_epilogue(const Args& a, const SpPhase& ph
     // accumulators go through LDS
     const bool fast = cdf_epi_tile_ok<BM, BN>(a, M) && cdf_epi_family_ok(a.epi, BFF);
     // (the K loop ends with a barrier: every wave is done with the operand tiles)
-    auto dump = [&]() {
-#pragma unroll
-        for (int i = 0; i < TM / 32; ++i)
-#pragma unroll
-            for (int j = 0; j < TN / 32; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    cs[(wm * TM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * half) * CP + wn * TN + j * 32 + l31] = acc[i][j][r];
-    };
+    auto dump = [&]() { cdf_acc_stage(cs, CP, wm * TM, wn * TN, acc, half, l31); };
     if (a.epi == CDF_EPI_LNBWD) {                            // (block-uniform; the host guarantees whole tiles and Cout == BN)
         cdf_epi_lnbwd<BM, BN, NTHR>(a, cs, tile_m, tid, dump);
         return;
@@ -169,6 +164,125 @@ __device__ __forceinline__ void cdf_mma_tile(f32x16_t (&acc)[MT][NT], const bf16
         }
     }
 }
+
+// ---- what the K loops of the pre-split forward kernels (k_conv_spx / k_conv_halo / k_conv_rowhalo.hip) share --------------------------------
+// Operand planes in LDS are [rows][CDF_SP_RE bf16 = 64 B], filled by LDS-DMA in 16-row segments (one wave instruction each) and XOR-swizzled
+// on both sides: the 16-byte column c of row r lives at column c ^ ((r >> 2) & 3).
+constexpr int CDF_SP_RE = 32;
+// this lane's DMA slot inside a segment: row lane >> 2, and the global 16-byte column (as an element offset) that lands in LDS column lane & 3
+__device__ __forceinline__ int cdf_dma_row(int lane) { return lane >> 2; }
+__device__ __forceinline__ int cdf_dma_col(int lane) { return ((lane & 3) ^ ((lane >> 4) & 3)) * 8; }
+// weight row n of a tile, clamped into the matrix (rows past Cout fetch the last row again; the epilogue never stores them) ...
+__device__ __forceinline__ int cdf_w_row(int n, int Cout) { return n < Cout ? n : Cout - 1; }
+// ... and the element offset of its K column k for weight slab (tap) wi
+__device__ __forceinline__ size_t cdf_w_off(int wi, int Cout, int row, int ldk, int k) {
+    return (size_t)((unsigned)wi * (unsigned)Cout + (unsigned)row) * (unsigned)ldk + (unsigned)k;
+}
+// the 16-row DMA segments of an R-row LDS image shared out over NW waves: wave w takes segments w + NW q, q < PER_WAVE; past NSEG it repeats
+// segment g mod NSEG -- same bytes to the same place, so that every wave issues the same number of DMA instructions and one wait count fits all
+template <int R, int NW>
+struct CdfDmaSegs {
+    static constexpr int NSEG = (R + 15) / 16, ROWS = NSEG * 16, PER_WAVE = (NSEG + NW - 1) / NW;
+    static __device__ __forceinline__ int seg(int wave, int q) {
+        int g = wave + NW * q;
+        if (g >= NSEG) g -= (g / NSEG) * NSEG;
+        return g;
+    }
+};
+// the first step of a de-phased ("late") wave multiplies zeros
+template <int MT, int NT>
+__device__ __forceinline__ void cdf_frag_zero(bf16x8_v (&ah)[2][MT], bf16x8_v (&al)[2][MT], bf16x8_v (&bh)[2][NT], bf16x8_v (&bl)[2][NT]) {
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+#pragma unroll
+        for (int i = 0; i < MT; ++i)
+#pragma unroll
+            for (int e = 0; e < 8; ++e) { ah[ks][i][e] = 0; al[ks][i][e] = 0; }
+#pragma unroll
+        for (int j = 0; j < NT; ++j)
+#pragma unroll
+            for (int e = 0; e < 8; ++e) { bh[ks][j][e] = 0; bl[ks][j][e] = 0; }
+    }
+}
+// Fragments of k-step ks out of a DMA-filled plane pair (hi at s, lo at s + PLANE): tile rows row + 32 t, t < T, where row = the wave's
+// first row + (lane & 31) and sw = ((lane & 31) >> 2) & 3 its swizzle (tile row offsets are multiples of 32)
+template <int NS, int PLANE, int T>
+__device__ __forceinline__ void cdf_read_frags(bf16x8_v (&fh)[T], bf16x8_v (&fl)[T], const unsigned short* s, int ks, int half, int row, int sw) {
+    const int kc = ((ks * 2 + half) ^ sw) * 8;
+#pragma unroll
+    for (int t = 0; t < T; ++t) {
+        const int off = (row + t * 32) * CDF_SP_RE + kc;
+        fh[t] = *(const bf16x8_v*)(s + off);
+        if constexpr (NS == 3) fl[t] = *(const bf16x8_v*)(s + PLANE + off);
+    }
+}
+// ... out of a row-pitched halo image: fragment t reads image rows rows[t] + shift (the tap's pixel offset), each with its own swizzle
+template <int NS, int PLANE, int T>
+__device__ __forceinline__ void cdf_read_frags_halo(bf16x8_v (&fh)[T], bf16x8_v (&fl)[T], const unsigned short* s, int ks, int half, const int (&rows)[T], int shift) {
+#pragma unroll
+    for (int t = 0; t < T; ++t) {
+        const int row = rows[t] + shift;
+        const int off = row * CDF_SP_RE + ((ks * 2 + half) ^ ((row >> 2) & 3)) * 8;
+        fh[t] = *(const bf16x8_v*)(s + off);
+        if constexpr (NS == 3) fl[t] = *(const bf16x8_v*)(s + PLANE + off);
+    }
+}
+// One K step of a wave.  De-phased waves (SpxArgs.dephase): the waves 4..7 of an 8-wave block share their SIMDs with waves 0..3 and the step
+// barrier keeps all eight in lockstep, so fragment reads / DMA issue (LDS, vector memory) and MFMAs (matrix pipe) of a SIMD's two waves used to
+// happen one after the other, never together.  A late wave therefore multiplies the fragments it read in the PREVIOUS step first and reads this
+// step's fragments afterwards: while one wave of a SIMD multiplies, the other one reads.  late is wave-uniform.
+template <class Read, class Mma>
+__device__ __forceinline__ void cdf_dephased_step(bool late, Read&& read, Mma&& mma) {
+    if (late) {
+        mma();
+        CDF_SCHED_FENCE();                                   // (the reads overwrite the fragments just multiplied: hoisting them doubles the live set)
+    }
+    read();
+    if (!late) mma();
+}
+
+// ---- LDS layouts: ONE statement per kernel form, read by the kernel (offsets, in bf16 elements) and by its launcher (bytes) --------------------
+constexpr size_t CDF_LDS_BYTES = 160 * 1024;
+constexpr int CDF_SP_PLANES = 2;                             // operand planes every stage reserves (hi, lo) -- the NS = 1 kernels too
+constexpr size_t cdf_max_sz(size_t a, size_t b) { return a > b ? a : b; }
+// generic kernel: NSTAGE x (A hi, A lo, B hi, B lo) | tap table; the epilogue tile [BM][BN + 8] floats aliases all of it
+template <int BM, int BN, int NSTAGE>
+struct SpxLayout {
+    static constexpr int PLANE_A = BM * CDF_SP_RE, PLANE_B = BN * CDF_SP_RE;
+    static constexpr int OFF_B = CDF_SP_PLANES * PLANE_A, STAGE = OFF_B + CDF_SP_PLANES * PLANE_B;
+    static constexpr int OFF_TAPS = NSTAGE * STAGE;          // CDF_MAX_TAPS + 1 ints
+    static constexpr size_t bytes = cdf_max_sz((size_t)OFF_TAPS * sizeof(unsigned short) + (CDF_MAX_TAPS + 1) * sizeof(int), (size_t)BM * (BN + 8) * sizeof(float));
+    static_assert(bytes <= CDF_LDS_BYTES, "tile does not fit the LDS");   // 128 x 128 x 2 stages: 68 KB (epilogue tile), two blocks per CU;
+};                                                                        // 256 x 128 x 3 stages: 144 KB, one block per CU
+// halo kernel: halo 0 | halo 1 | NB weight stages (as many as fit, at most 6); the epilogue tile aliases all of it
+template <int W, int BN, int BM>
+struct HaloLayout {
+    static constexpr int TH = BM / W, HW2 = W + 2, HR = (TH + 2) * HW2;   // halo rows (pixels)
+    typedef CdfDmaSegs<HR, 8> Segs;
+    static constexpr int PLANE_A = Segs::ROWS * CDF_SP_RE, ABUF = CDF_SP_PLANES * PLANE_A;
+    static constexpr int PLANE_B = BN * CDF_SP_RE, BSTAGE = CDF_SP_PLANES * PLANE_B;
+    static constexpr int OFF_B = 2 * ABUF;
+    static constexpr int NBfit = (int)((CDF_LDS_BYTES - 64 - OFF_B * sizeof(unsigned short)) / (BSTAGE * sizeof(unsigned short)));
+    static constexpr int NB = NBfit > 6 ? 6 : NBfit;
+    static_assert(NB >= 3, "halo tile leaves no room for three weight stages");
+    static constexpr size_t bytes = cdf_max_sz((size_t)(OFF_B + NB * BSTAGE) * sizeof(unsigned short) + 16 * sizeof(int), (size_t)BM * (BN + 8) * sizeof(float));
+    static_assert(bytes <= CDF_LDS_BYTES, "halo tile does not fit the LDS");
+};
+// row-halo stream kernel: rows 0 | weights 0 | weights 1 | rows 1 | weights 2 | ...; the staging tile [EROWS][BN + 8] floats starts at "rows 1":
+// it aliases only what is idle during the epilogue (rows 1, weights 2 and the tail)
+template <int W, int BN, int BM = 256>
+struct RowHaloLayout {
+    static constexpr int TH = BM / W, HW2 = W + 2, RH = TH * HW2;
+    typedef CdfDmaSegs<RH, 8> Segs;
+    static constexpr int PLANE_A = Segs::ROWS * CDF_SP_RE, ABUF = CDF_SP_PLANES * PLANE_A;
+    static constexpr int PLANE_B = BN * CDF_SP_RE, BSTAGE = CDF_SP_PLANES * PLANE_B;
+    static constexpr int OFF_A1 = ABUF + 2 * BSTAGE, OFF_B2 = OFF_A1 + ABUF, OFF_CS = OFF_A1;
+    static constexpr int EROWS = BM / 2, CP = BN + 8;        // rows per epilogue pass, staging pitch
+    static constexpr int a_off(int buf) { return buf ? OFF_A1 : 0; }
+    static constexpr int b_off(int stage) { return stage == 2 ? OFF_B2 : ABUF + stage * BSTAGE; }
+    static constexpr size_t bytes = (size_t)OFF_CS * sizeof(unsigned short) + cdf_max_sz((size_t)(ABUF + BSTAGE) * sizeof(unsigned short), (size_t)EROWS * CP * sizeof(float));
+    static_assert(bytes <= CDF_LDS_BYTES, "streaming row-halo tile does not fit the LDS");
+};
 
 // XCD-aware block order of the weight-gradient grids (tiles, taps, splits).  Workgroups go to the 8 XCDs round-robin in
 // dispatch order, so the taps of one pixel range (next to each other in dispatch order) would land on 8 different L2s

@@ -70,8 +70,7 @@ __global__ void __launch_bounds__(256) linattn_ctx_kernel(const float* a_ptr, in
     const float* A = a_ptr + (long long)b * n * lda + h * LA_D + i;
     const float* Bp = b_ptr + (long long)b * n * ldb + h * LA_D + i;
     f32x16_t acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+    cdf_acc_zero(acc);
     float psum = 0.f;
     // each wave takes row pairs r0 + 2*(wave + 4*j); four pairs per trip with all 8 loads in flight, unconditional
     // (clamped row + select: a load behind a divergent branch waits for everything before it)
@@ -92,8 +91,7 @@ __global__ void __launch_bounds__(256) linattn_ctx_kernel(const float* a_ptr, in
         }
     }
     psum += __shfl_xor(psum, 32);
-#pragma unroll
-    for (int r = 0; r < 16; ++r) red[wave][((r & 3) + 8 * (r >> 2) + 4 * hh) * LA_D + i] = acc[r];
+    cdf_acc_stage(red[wave], LA_D, 0, 0, acc, hh, i);
     if (hh == 0) sred[wave][i] = psum;
     __syncthreads();
     float* dst = ctx_part + ((((long long)b * gridDim.y + split) * heads + h) * LA_D) * LA_D;
@@ -170,16 +168,14 @@ __global__ void __launch_bounds__(256) linattn_ctx1p_kernel(const float* kv, int
     // ctx_part[d][e] = sum_rows P~[row][d] v[row][e]: wave w takes rows 64 w .. 64 w + 63
     const int i = lane & 31, hh = lane >> 5;
     f32x16_t acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+    cdf_acc_zero(acc);
     const float* ap = sp + (wave * 64 + hh) * LA_D + i;
     const float* bp = sv + (wave * 64 + hh) * LA_D + i;
 #pragma unroll 8
     for (int s = 0; s < 32; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ap[2 * s * LA_D], bp[2 * s * LA_D], acc, 0, 0, 0);
     __syncthreads();                              // every wave is done reading sp / sv (and the sums in red)
     float* rw = sp + wave * (LA_D * LA_D);            // (the four accumulator tiles reuse the P~ tile)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) rw[((r & 3) + 8 * (r >> 2) + 4 * hh) * LA_D + i] = acc[r];
+    cdf_acc_stage(rw, LA_D, 0, 0, acc, hh, i);
     __syncthreads();
     float* dst = ctx_part + (pb * heads + h) * (LA_D * LA_D);
     for (int k = tid; k < LA_D * LA_D; k += 256)
@@ -364,15 +360,6 @@ __global__ void softmax_rows_bwd_kernel(const float* p, const float* dp, float* 
 // ================================================================================================
 // C ABI
 // ================================================================================================
-static void la_final_attr() {
-#ifndef CDF_EMU
-    static CdfDeviceLatch done;
-    if (done.first()) {          // nsplit x 128 B of rescaling weights next to ~4 KB of static LDS: past the 64 KB default from ~480 partials up
-        (void)hipFuncSetAttribute((const void*)linattn_ctx1p_final_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);   // (+ ~4 KB static: the sum must stay under the 160 KB of a CU)
-    }
-#endif
-}
-
 extern "C" int cdf_linattn_nsplit(int n) {       // 256 rows per split (the one-pass context kernel holds a split's k, v tile in LDS)
     int s = (n + 255) / 256;
     if (s < 1) s = 1;
@@ -399,15 +386,10 @@ extern "C" int cdf_linattn_context(const float* qkv, int ld, int koff, float* ct
     float* sum_part = ctx_part + (size_t)B * ns * heads * LA_D * LA_D;
     if (onepass && ns <= 1024) {
         const size_t lds = ((size_t)2 * 256 * LA_D + 32 * LA_D + LA_D) * sizeof(float);
-#ifndef CDF_EMU
-        static CdfDeviceLatch attr_done;
-        if (attr_done.first()) {
-            (void)hipFuncSetAttribute((const void*)linattn_ctx1p_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        }
-#endif
-        CDF_LAUNCH(linattn_ctx1p_kernel, dim3(heads, ns, B), dim3(256), lds, CDF_S, qkv, ld, koff, kmax_part, ctx_part, sum_part, n, HD);
-        la_final_attr();
-        CDF_LAUNCH(linattn_ctx1p_final_kernel, dim3(heads, B), dim3(1024), (size_t)ns * LA_D * sizeof(float), CDF_S, (const float*)ctx_part,
+        CDF_LAUNCH_LDS(linattn_ctx1p_kernel, dim3(heads, ns, B), dim3(256), lds, CDF_S, qkv, ld, koff, kmax_part, ctx_part, sum_part, n, HD);
+        // nsplit x 128 B of rescaling weights next to ~4 KB of static LDS: past the 64 KB default from ~480 partials up (limit 128 KB: with
+        // the static part the sum must stay under the 160 KB of a CU)
+        CDF_LAUNCH_LDS_MAX(128 * 1024, linattn_ctx1p_final_kernel, dim3(heads, B), dim3(1024), (size_t)ns * LA_D * sizeof(float), CDF_S, (const float*)ctx_part,
                    (const float*)sum_part, (const float*)kmax_part, ns, HD, ctx, ctxs, scale, kmax, ksum);
         return cdf_check_launch("linattn_context");
     }
@@ -426,8 +408,7 @@ extern "C" int cdf_linattn_finalize(const float* ws, int nparts, float* ctx, flo
     const float* max_part = ws;
     const float* ctx_part = max_part + (size_t)B * nparts * HD;
     const float* sum_part = ctx_part + (size_t)B * nparts * heads * LA_D * LA_D;
-    la_final_attr();
-    CDF_LAUNCH(linattn_ctx1p_final_kernel, dim3(heads, B), dim3(1024), (size_t)nparts * LA_D * sizeof(float), CDF_S, ctx_part, sum_part, max_part,
+    CDF_LAUNCH_LDS_MAX(128 * 1024, linattn_ctx1p_final_kernel, dim3(heads, B), dim3(1024), (size_t)nparts * LA_D * sizeof(float), CDF_S, ctx_part, sum_part, max_part,
                nparts, HD, ctx, ctxs, scale, kmax, ksum);
     return cdf_check_launch("linattn_finalize");
 }
@@ -544,13 +525,12 @@ __global__ void __launch_bounds__(256) linattn_bwd_kv_kernel(const float* qkv, i
         CDF_WAVE_SYNC();                                   // (one wave owns these tiles: LDS operations of a wave are in order)
         // ---- dP = V dctx^T ; dk = P (dP - rvec)
         f32x16_t acc;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+        cdf_acc_zero(acc);
 #pragma unroll
         for (int s = 0; s < 16; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(sv[i * LA_TP + 2 * s + hh], B1[s], acc, 0, 0, 0);
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int px = (r & 3) + 8 * (r >> 2) + 4 * hh;                // accumulator row of this lane's column d = i
+            const int px = cdf_acc_row(r, hh);                // accumulator row of this lane's column d = i
             so[px * LA_TP + i] = sp[px * LA_TP + i] * (acc[r] - rv);
         }
         CDF_WAVE_SYNC();
@@ -561,12 +541,11 @@ __global__ void __launch_bounds__(256) linattn_bwd_kv_kernel(const float* qkv, i
         }
         CDF_WAVE_SYNC();
         // ---- dv = P dctx
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+        cdf_acc_zero(acc);
 #pragma unroll
         for (int s = 0; s < 16; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(sp[i * LA_TP + 2 * s + hh], B2[s], acc, 0, 0, 0);
 #pragma unroll
-        for (int r = 0; r < 16; ++r) so[((r & 3) + 8 * (r >> 2) + 4 * hh) * LA_TP + i] = acc[r];
+        for (int r = 0; r < 16; ++r) so[cdf_acc_row(r, hh) * LA_TP + i] = acc[r];
         CDF_WAVE_SYNC();
 #pragma unroll
         for (int q = 0; q < 4; ++q) {

@@ -194,12 +194,7 @@ __global__ void __launch_bounds__(256, 4) conv_igemm_kernel(ConvArgs a) {
     };
 
     f32x16_t acc[MT][NT];
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < NT; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    cdf_acc_zero(acc);
 
     const int half = lane >> 5, l31 = lane & 31;
     if (niter > 0) {
@@ -242,7 +237,7 @@ __global__ void __launch_bounds__(256, 4) conv_igemm_kernel(ConvArgs a) {
         for (int j = 0; j < NT; ++j)
 #pragma unroll
             for (int r = 0; r < 16; ++r)
-                smem[(wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * half) * CP + wn * WN + j * 32 + l31] = acc[i][j][r];
+                smem[(wm * 32 + cdf_acc_row(r, half)) * CP + wn * WN + j * 32 + l31] = acc[i][j][r];
         __syncthreads();
         cdf_epilogue_rows<BN, EPI_ROWS>(a, ph, Y, smem, tile_m * BM, tile_n * BN, M, tid,
                                         [i](int p) { return (p >> 5) * WM + i * 32 + (p & 31); }, pix_off);
@@ -384,12 +379,7 @@ __global__ void __launch_bounds__(256, 4) conv_wgrad_kernel(WgradArgs a) {
     };
 
     f32x16_t acc[MT][NT];
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < NT; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    cdf_acc_zero(acc);
 
     const int half = lane >> 5, l31 = lane & 31;
     if (niter > 0) {
@@ -445,7 +435,7 @@ __global__ void __launch_bounds__(256, 4) conv_wgrad_kernel(WgradArgs a) {
     for (int i = 0; i < MT; ++i)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int ca = tile_a * BMC + wm * WM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+            const int ca = tile_a * BMC + wm * WM + i * 32 + cdf_acc_row(r, half);
             if (ca >= a.CA) continue;
 #pragma unroll
             for (int j = 0; j < NT; ++j) {

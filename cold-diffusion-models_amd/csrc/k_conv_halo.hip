@@ -27,21 +27,22 @@ constexpr int cdf_halo_parts(int t, int n, int ta) {
 
 template <int W, int BN, int NB, int BM, int NS = 3>                    // NB weight stages: NB - 1 tap steps requested ahead; BM = 128 or 256 pixels
 __global__ void __launch_bounds__(512, 1) conv_igemm_halo_kernel(SpxArgs a) {
-    constexpr int WM = 4, WN = 2, NW = 8, BK = 32, RE = 32, MT = BM / WM / 32;
-    constexpr int TH = BM / W, HW2 = W + 2, HR = (TH + 2) * HW2;          // halo rows (pixels)
-    constexpr int NSEG = (HR + 15) / 16, HRP = NSEG * 16;                 // 16-row DMA segments
-    constexpr int TA = (NSEG + NW - 1) / NW;                              // tap steps in which a wave fetches one A segment
+    constexpr int WM = 4, WN = 2, NW = 8, BK = 32, RE = CDF_SP_RE, MT = BM / WM / 32;
+    using L = HaloLayout<W, BN, BM>;
+    using Segs = typename L::Segs;                                        // 16-row DMA segments of the halo image
+    static_assert(NB == L::NB, "the launcher instantiates the stage count of the layout");
+    constexpr int TH = L::TH, HW2 = L::HW2, HR = L::HR;
+    constexpr int TA = Segs::PER_WAVE;                                    // tap steps in which a wave fetches one A segment
     static_assert(NB >= 3 && NB <= 7 && TA <= 11 - NB && TA <= 12 - NB, "the next chunk's halo must be requested before the weights of its first tap");
     constexpr int NT = BN / WN / 32;                                      // 32 x 32 MFMA tiles per wave along N (M: 1)
     constexpr int SB = BN / 16 / NW;                                      // B segments per wave and plane (1 for BN = 128)
     static_assert(SB * NW * 16 == BN || BN == 64, "B tile must split into 16-row segments");
     constexpr int SBI = BN == 64 ? 1 : SB;                                // (BN = 64: waves 0..3 fetch a segment, 4..7 repeat them)
-    constexpr int PLANE_A = HRP * RE, ABUF = 2 * PLANE_A;                 // (unsigned short units)
-    constexpr int PLANE_B = BN * RE, BSTAGE = 2 * PLANE_B;
+    constexpr int PLANE_A = L::PLANE_A, ABUF = L::ABUF, PLANE_B = L::PLANE_B, BSTAGE = L::BSTAGE;   // (unsigned short units)
     CDF_DYN_SMEM(smem_raw);
     unsigned short* smem = (unsigned short*)smem_raw;
     unsigned short* const abuf0 = smem;
-    unsigned short* const bst0 = smem + 2 * ABUF;
+    unsigned short* const bst0 = smem + L::OFF_B;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave / WN, wn = wave % WN;
@@ -56,18 +57,14 @@ __global__ void __launch_bounds__(512, 1) conv_igemm_halo_kernel(SpxArgs a) {
     // (tap indices are compile-time constants in the unrolled loops below: ph.dy[t] etc. are scalar kernel-argument loads
     // hoisted out of the K loop -- an LDS tap table would put an lgkmcnt(0) wait between the fragment reads and the MFMAs)
 
-    // ---- DMA sources.  A: segment g = wave + 8 q (q < TA; past NSEG the wave repeats segment g mod NSEG -- same bytes to
-    // the same place, so that every wave issues the same number of DMA instructions per step and one s_waitcnt count fits all)
-    const int srow = lane >> 2;
-    const int q8 = ((lane & 3) ^ ((lane >> 4) & 3)) * 8;
+    // ---- DMA sources.  A: segments Segs::seg(wave, q), q < TA
+    const int srow = cdf_dma_row(lane), q8 = cdf_dma_col(lane);
     const unsigned short* pa_hi[TA];
     const unsigned short* pa_lo[TA];
     int a_inc[TA], a_seg[TA];
 #pragma unroll
     for (int q = 0; q < TA; ++q) {
-        int g = wave + NW * q;
-        if (g >= NSEG) g -= (g / NSEG) * NSEG;
-        a_seg[q] = g;
+        const int g = a_seg[q] = Segs::seg(wave, q);
         const int r = g * 16 + srow;
         const int hy = r / HW2, hx = r - hy * HW2;
         const int y = y0 - 1 + hy, x = hx - 1;
@@ -81,8 +78,7 @@ __global__ void __launch_bounds__(512, 1) conv_igemm_halo_kernel(SpxArgs a) {
 #pragma unroll
     for (int p = 0; p < SBI; ++p) {
         const int seg = BN == 64 ? (wave & 3) : wave * SB + p;
-        const int n = tile_n * BN + seg * 16 + srow;
-        b_row[p] = n < a.Cout ? n : a.Cout - 1;
+        b_row[p] = cdf_w_row(tile_n * BN + seg * 16 + srow, a.Cout);
     }
     const int nchunks = a.Cin / BK;
 
@@ -105,7 +101,7 @@ __global__ void __launch_bounds__(512, 1) conv_igemm_halo_kernel(SpxArgs a) {
 #pragma unroll
         for (int p = 0; p < SBI; ++p) {
             const int seg = BN == 64 ? (wave & 3) : wave * SB + p;
-            const size_t woff = (size_t)((unsigned)wi * (unsigned)a.Cout + (unsigned)b_row[p]) * (unsigned)a.ldk + (unsigned)(c * BK + q8);
+            const size_t woff = cdf_w_off(wi, a.Cout, b_row[p], a.ldk, c * BK + q8);
             CDF_GLDS16_K(a.w_hi + woff, st + seg * 16 * RE);
             if constexpr (NS == 3) CDF_GLDS16_K(a.w_lo + woff, st + PLANE_B + seg * 16 * RE);
         }
@@ -114,12 +110,7 @@ __global__ void __launch_bounds__(512, 1) conv_igemm_halo_kernel(SpxArgs a) {
     constexpr int PB = NPL * SBI, PA = NPL;                  // DMA instructions per wave: one B step, one A segment
 
     f32x16_t acc[MT][NT];
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < NT; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    cdf_acc_zero(acc);
 
     const int half = lane >> 5, l31 = lane & 31;
     // this lane's A fragment rows for tap (0, 0): pixels p = (BM/4) wm + 32 i + l31 of the tile
@@ -143,19 +134,7 @@ __global__ void __launch_bounds__(512, 1) conv_igemm_halo_kernel(SpxArgs a) {
     CDF_LDS_BARRIER();
     bf16x8_v ah[2][MT], al[2][MT], bh[2][NT], bl[2][NT];
     const bool late = a.dephase != 0 && wave >= NW / 2;      // (wave-uniform)
-    if (late) {                                              // first step of a late wave: multiplies zeros
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-#pragma unroll
-            for (int i = 0; i < MT; ++i)
-#pragma unroll
-                for (int e = 0; e < 8; ++e) { ah[ks][i][e] = 0; al[ks][i][e] = 0; }
-#pragma unroll
-            for (int j = 0; j < NT; ++j)
-#pragma unroll
-                for (int e = 0; e < 8; ++e) { bh[ks][j][e] = 0; bl[ks][j][e] = 0; }
-        }
-    }
+    if (late) cdf_frag_zero(ah, al, bh, bl);
     auto mma_frags = [&]() { cdf_mma_tile<NS, MT, NT>(acc, ah, al, bh, bl); };
     for (int c = 0; c < nchunks; ++c) {
         const unsigned short* sa = abuf0 + (c & 1) * ABUF;
@@ -172,32 +151,11 @@ __global__ void __launch_bounds__(512, 1) conv_igemm_halo_kernel(SpxArgs a) {
             auto read_frags = [&]() {
 #pragma unroll
                 for (int ks = 0; ks < 2; ++ks) {
-#pragma unroll
-                    for (int i = 0; i < MT; ++i) {
-                        const int row = row0[i] + tapoff;
-                        const int off = row * RE + ((ks * 2 + half) ^ ((row >> 2) & 3)) * 8;
-                        ah[ks][i] = *(const bf16x8_v*)(sa + off);
-                        if constexpr (NS == 3) al[ks][i] = *(const bf16x8_v*)(sa + PLANE_A + off);
-                    }
-                    const int kc = ((ks * 2 + half) ^ swb) * 8;
-#pragma unroll
-                    for (int j = 0; j < NT; ++j) {
-                        const int offb = (wn * (BN / WN) + j * 32 + l31) * RE + kc;
-                        bh[ks][j] = *(const bf16x8_v*)(sb + offb);
-                        if constexpr (NS == 3) bl[ks][j] = *(const bf16x8_v*)(sb + PLANE_B + offb);
-                    }
+                    cdf_read_frags_halo<NS, PLANE_A>(ah[ks], al[ks], sa, ks, half, row0, tapoff);
+                    cdf_read_frags<NS, PLANE_B>(bh[ks], bl[ks], sb, ks, half, wn * (BN / WN) + l31, swb);
                 }
             };
-            // De-phased waves (a.dephase): the block's waves 4..7 share their SIMDs with waves 0..3 and the step barrier keeps all
-            // eight in lockstep, so fragment reads (LDS) and MFMAs (matrix pipe) of a SIMD's two waves used to happen one after the
-            // other, never together.  Waves 4..7 therefore multiply the fragments they read in the PREVIOUS step first and read this
-            // step's fragments afterwards: while one wave of a SIMD multiplies, the other one reads.
-            if (late) {
-                mma_frags();
-                CDF_SCHED_FENCE();                           // (the reads overwrite the fragments just multiplied: hoisting them doubles the live set)
-            }
-            read_frags();
-            if (!late) mma_frags();
+            cdf_dephased_step(late, read_frags, mma_frags);
             // the weights of step + 1 (requested NB - 2 steps ago) have landed -- and with them, in order, every halo segment
             // requested before them; still in flight: the weight requests of the last NB - 2 steps and the halo segments
             // requested in those steps (a compile-time count per tap index)
@@ -221,28 +179,12 @@ __global__ void __launch_bounds__(512, 1) conv_igemm_halo_kernel(SpxArgs a) {
 
 template <int NS, int W, int BN, int BM>
 static int launch_igemm_halo(const SpxArgs& a, int M, hipStream_t s, CdfPlan* plan) {
-    // weight stages: as many as fit next to the two halo buffers
-    constexpr int TH = BM / W, HR = (TH + 2) * (W + 2), HRP = (HR + 15) / 16 * 16;
-    constexpr size_t abytes = (size_t)2 * 2 * HRP * 64, bstage = (size_t)2 * BN * 64;
-    constexpr int NBfit = (int)((160 * 1024 - 64 - abytes) / bstage);
-    constexpr int NB = NBfit > 6 ? 6 : NBfit;
-    static_assert(NB >= 3, "halo tile leaves no room for three weight stages");
-    constexpr size_t stages = abytes + (size_t)NB * bstage + 16 * sizeof(int);
-    constexpr size_t epi = (size_t)BM * (BN + 8) * sizeof(float);
-    constexpr size_t lds = stages > epi ? stages : epi;
-    static_assert(lds <= 160 * 1024, "halo tile does not fit the LDS");
+    using L = HaloLayout<W, BN, BM>;
     const int tiles = (M / BM) * cdf_cdiv(a.Cout, BN);
-    if (plan) return cdf_plan_set(plan, CDF_FORM_HALO, BM, BN, NB, 1, W, tiles, tiles);
-#ifndef CDF_EMU
-    static CdfDeviceLatch attr_done;
-    if (attr_done.first()) {
-        (void)hipFuncSetAttribute((const void*)conv_igemm_halo_kernel<W, BN, NB, BM, NS>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    }
-#endif
-    CDF_LAUNCH((conv_igemm_halo_kernel<W, BN, NB, BM, NS>), dim3(tiles), dim3(512), lds, s, a);
+    if (plan) return cdf_plan_set(plan, CDF_FORM_HALO, BM, BN, L::NB, 1, W, tiles, tiles);
+    CDF_LAUNCH_LDS((conv_igemm_halo_kernel<W, BN, L::NB, BM, NS>), dim3(tiles), dim3(512), L::bytes, s, a);
     return cdf_check_launch("conv_igemm_halo");
 }
-
 
 template <int NS>
 static int launch_halo_ns(int W, bool n64, int bm, const SpxArgs& a, int M, hipStream_t s, CdfPlan* plan) {

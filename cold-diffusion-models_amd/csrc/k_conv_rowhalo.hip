@@ -26,25 +26,22 @@
 // ================================================================================================
 template <int W, int BN, int NS = 3, int NCH = 2, int BM = 256>
 __global__ void __launch_bounds__(512, 1) conv_igemm_rowhalo_stream_kernel(SpxArgs a) {
-    constexpr int WM = BM / 64, WN = 8 / WM, NW = 8, BK = 32, RE = 32, MT = BM / WM / 32, NB = 3;
+    constexpr int WM = BM / 64, WN = 8 / WM, NW = 8, BK = 32, RE = CDF_SP_RE, MT = BM / WM / 32, NB = 3;
     static_assert(BM == 256 && WM * WN == 8 && MT == 2, "8 waves (4 x 2) of 64-row tiles");
     static_assert(NCH % 2 == 0, "an even number of tap-row groups per tile returns the pipeline to row buffer 0");
-    constexpr int EROWS = BM / 2;                                                 // rows per epilogue pass
-    constexpr int TH = BM / W, HW2 = W + 2, RH = TH * HW2;
-    constexpr int NSEG = (RH + 15) / 16, HRP = NSEG * 16;
-    constexpr int TAG = (NSEG + NW - 1) / NW;
+    using L = RowHaloLayout<W, BN, BM>;
+    using Segs = typename L::Segs;
+    constexpr int EROWS = L::EROWS, CP = L::CP;                                  // rows per epilogue pass, staging pitch
+    constexpr int TH = L::TH, HW2 = L::HW2, RH = L::RH;
+    constexpr int TAG = Segs::PER_WAVE;
     constexpr int NT = BN / WN / 32;
     constexpr int SB = BN / 16 / NW;
     static_assert(SB * NW * 16 == BN || BN == 64, "B tile must split into 16-row segments");
     constexpr int SBI = BN == 64 ? 1 : SB;
-    constexpr int PLANE_A = HRP * RE, ABUF = 2 * PLANE_A;
-    constexpr int PLANE_B = BN * RE, BSTAGE = 2 * PLANE_B;
-    constexpr int OFF_A1 = ABUF + 2 * BSTAGE, OFF_B2 = OFF_A1 + ABUF;          // (elements) rows 0 | weights 0 | weights 1 | rows 1 | weights 2
+    constexpr int PLANE_A = L::PLANE_A, PLANE_B = L::PLANE_B;
     CDF_DYN_SMEM(smem_raw);
     unsigned short* smem = (unsigned short*)smem_raw;
-    float* const cs = (float*)(smem + OFF_A1);                                   // epilogue staging: rows 1, weights 2 and the tail are idle then
-    constexpr int CP = BN + 8;
-    static_assert((size_t)OFF_A1 * 2 + (size_t)EROWS * CP * 4 <= 160 * 1024, "the staging tile must fit behind the live operand buffers");
+    float* const cs = (float*)(smem + L::OFF_CS);                                // epilogue staging: rows 1, weights 2 and the tail are idle then
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave / WN, wn = wave % WN;
@@ -53,21 +50,18 @@ __global__ void __launch_bounds__(512, 1) conv_igemm_rowhalo_stream_kernel(SpxAr
     const SpPhase& ph = a.ph[0];
     const int tpi = a.H / TH;
 
-    const int srow = lane >> 2;
-    const int q8 = ((lane & 3) ^ ((lane >> 4) & 3)) * 8;
+    const int srow = cdf_dma_row(lane), q8 = cdf_dma_col(lane);
     int a_seg[TAG], a_ry[TAG], a_x[TAG];
 #pragma unroll
     for (int q = 0; q < TAG; ++q) {
-        int g = wave + NW * q;
-        if (g >= NSEG) g -= (g / NSEG) * NSEG;
-        a_seg[q] = g;
+        const int g = a_seg[q] = Segs::seg(wave, q);
         const int r = g * 16 + srow;
         a_ry[q] = r < RH ? r / HW2 : -(1 << 20);
         a_x[q] = r - (r / HW2) * HW2 - 1;
     }
     // rows of (tile position (img, y0), chunk c, tap row offset dy) -> row buffer buf; img < 0: no such tile, zero page
     auto fetch_a = [&](int img, int y0, int c, int dy, int buf) {
-        unsigned short* base = smem + (buf ? OFF_A1 : 0);
+        unsigned short* base = smem + L::a_off(buf);
 #pragma unroll
         for (int q = 0; q < TAG; ++q) {
             const int y = y0 + a_ry[q] + dy;
@@ -79,13 +73,11 @@ __global__ void __launch_bounds__(512, 1) conv_igemm_rowhalo_stream_kernel(SpxAr
         }
     };
     auto fetch_b = [&](int tile_n, int c, int wi, int stage) {       // weights of (N tile, chunk c, tap with weight index wi) -> stage
-        unsigned short* st = smem + (stage == 2 ? OFF_B2 : ABUF + stage * BSTAGE);
+        unsigned short* st = smem + L::b_off(stage);
 #pragma unroll
         for (int p = 0; p < SBI; ++p) {
             const int seg = BN == 64 ? (wave & 3) : wave * SB + p;
-            const int n = tile_n * BN + seg * 16 + srow;
-            const int brow = n < a.Cout ? n : a.Cout - 1;
-            const size_t woff = (size_t)((unsigned)wi * (unsigned)a.Cout + (unsigned)brow) * (unsigned)a.ldk + (unsigned)(c * BK + q8);
+            const size_t woff = cdf_w_off(wi, a.Cout, cdf_w_row(tile_n * BN + seg * 16 + srow, a.Cout), a.ldk, c * BK + q8);
             CDF_GLDS16_K(a.w_hi + woff, st + seg * 16 * RE);
             if constexpr (NS == 3) CDF_GLDS16_K(a.w_lo + woff, st + PLANE_B + seg * 16 * RE);
         }
@@ -129,26 +121,9 @@ __global__ void __launch_bounds__(512, 1) conv_igemm_rowhalo_stream_kernel(SpxAr
         int img_n, y0_n, tile_n_n, tile_m_n;
         tile_pos(v + gridDim.x, img_n, y0_n, tile_n_n, tile_m_n);
         f32x16_t acc[MT][NT];
-#pragma unroll
-        for (int i = 0; i < MT; ++i)
-#pragma unroll
-            for (int j = 0; j < NT; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+        cdf_acc_zero(acc);
         bf16x8_v ah[2][MT], al[2][MT], bh[2][NT], bl[2][NT];
-        if (late) {
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-#pragma unroll
-                for (int i = 0; i < MT; ++i)
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) { ah[ks][i][e] = 0; al[ks][i][e] = 0; }
-#pragma unroll
-                for (int j = 0; j < NT; ++j)
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) { bh[ks][j][e] = 0; bl[ks][j][e] = 0; }
-            }
-        }
+        if (late) cdf_frag_zero(ah, al, bh, bl);
         auto mma_frags = [&]() { cdf_mma_tile<NS, MT, NT>(acc, ah, al, bh, bl); };
         // The lane's fragment rows, through an opaque register once per tile: every fragment address of the unrolled K loop derives from
         // them and is tile-invariant, so hipcc kept ~80 precomputed addresses live across the whole tile loop -- EPILOGUE included, where
@@ -188,7 +163,7 @@ __global__ void __launch_bounds__(512, 1) conv_igemm_rowhalo_stream_kernel(SpxAr
                     }
                     // (the buffer bases as opaque scalars: as constants beyond the 64 KB reach of a ds_read immediate they made hipcc keep one
                     //  precomputed fragment address per (buffer, dx, fragment) live across the whole tile loop -- 58 VGPRs spilled)
-                    int sa_e = par ? OFF_A1 : 0, sb_e = rd == 2 ? OFF_B2 : ABUF + rd * BSTAGE;
+                    int sa_e = L::a_off(par), sb_e = L::b_off(rd);
 #ifndef CDF_EMU
                     asm volatile("" : "+s"(sa_e), "+s"(sb_e));
 #endif
@@ -198,28 +173,11 @@ __global__ void __launch_bounds__(512, 1) conv_igemm_rowhalo_stream_kernel(SpxAr
                     auto read_frags = [&]() {
 #pragma unroll
                         for (int ks = 0; ks < 2; ++ks) {
-#pragma unroll
-                            for (int i = 0; i < MT; ++i) {
-                                const int row = row0t[i] + dx;
-                                const int off = row * RE + ((ks * 2 + half) ^ ((row >> 2) & 3)) * 8;
-                                ah[ks][i] = *(const bf16x8_v*)(sa + off);
-                                if constexpr (NS == 3) al[ks][i] = *(const bf16x8_v*)(sa + PLANE_A + off);
-                            }
-                            const int kc = ((ks * 2 + half) ^ swbt) * 8;
-#pragma unroll
-                            for (int j = 0; j < NT; ++j) {
-                                const int offb = (wn * (BN / WN) + j * 32 + l31t) * RE + kc;
-                                bh[ks][j] = *(const bf16x8_v*)(sb + offb);
-                                if constexpr (NS == 3) bl[ks][j] = *(const bf16x8_v*)(sb + PLANE_B + offb);
-                            }
+                            cdf_read_frags_halo<NS, PLANE_A>(ah[ks], al[ks], sa, ks, half, row0t, dx);
+                            cdf_read_frags<NS, PLANE_B>(bh[ks], bl[ks], sb, ks, half, wn * (BN / WN) + l31t, swbt);
                         }
                     };
-                    if (late) {
-                        mma_frags();
-                        CDF_SCHED_FENCE();
-                    }
-                    read_frags();
-                    if (!late) mma_frags();
+                    cdf_dephased_step(late, read_frags, mma_frags);
                     // the weights of step + 1 have landed (requested one step ago, before that step's row request); may still be in
                     // flight: this step's weights and the rows requested in this group's first step -- those only at the group's end not
                     if (i3 <= 1)
@@ -241,14 +199,7 @@ __global__ void __launch_bounds__(512, 1) conv_igemm_rowhalo_stream_kernel(SpxAr
 #ifndef CDF_EMU
                 asm volatile("" : "+v"(base));
 #endif
-                float* cb = cs + base;
-#pragma unroll
-                for (int i = 0; i < MT; ++i)
-#pragma unroll
-                    for (int j = 0; j < NT; ++j)
-#pragma unroll
-                        for (int r = 0; r < 16; ++r)
-                            cb[(i * 32 + (r & 3) + 8 * (r >> 2)) * CP + j * 32] = acc[i][j][r];
+                cdf_acc_stage(cs + base, CP, 0, 0, acc, 0, 0);       // (the lane's row half and column are in base)
             }
         };
         if (fast_epi) {
@@ -288,17 +239,7 @@ __global__ void __launch_bounds__(512, 1) conv_igemm_rowhalo_stream_kernel(SpxAr
 
 template <int NS, int W, int BN>
 static int launch_igemm_rowhalo_stream(const SpxArgs& a, int M, hipStream_t s, int reserve, CdfPlan* plan) {
-    constexpr int TH = 256 / W, RH = TH * (W + 2), HRP = (RH + 15) / 16 * 16;
-    constexpr size_t st_a = (size_t)2 * HRP * 64, st_b = (size_t)2 * BN * 64;
-    constexpr size_t lds_s = (st_a + 2 * st_b) + ((st_a + st_b) > (size_t)128 * (BN + 8) * 4 ? (st_a + st_b) : (size_t)128 * (BN + 8) * 4);
-    static_assert(lds_s <= 160 * 1024, "streaming row-halo tile does not fit the LDS");
-#ifndef CDF_EMU
-    static CdfDeviceLatch attr_done;
-    if (!plan && attr_done.first()) {
-        (void)hipFuncSetAttribute((const void*)conv_igemm_rowhalo_stream_kernel<W, BN, NS, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)conv_igemm_rowhalo_stream_kernel<W, BN, NS, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    }
-#endif
+    using L = RowHaloLayout<W, BN>;
     const int tiles = (M / 256) * cdf_cdiv(a.Cout, BN);
     // resident blocks: one per CU -- minus the CUs the caller keeps free for kernels that run concurrently (cdf_gemm_tuning.resident_reserve:
     // the collectives of a multi-rank gradient exchange; a resident block that finds its CU taken would run its fixed share of the tiles
@@ -313,9 +254,9 @@ static int launch_igemm_rowhalo_stream(const SpxArgs& a, int M, hipStream_t s, i
     const int grid = tiles < ncu ? tiles : ncu;
     if (plan) return cdf_plan_set(plan, CDF_FORM_ROWHALO, 256, BN, a.Cin == 64 ? 2 : 4, 1, W, tiles, grid);   // ("stages": channel chunks per tap row)
     if (a.Cin == 64)
-        CDF_LAUNCH((conv_igemm_rowhalo_stream_kernel<W, BN, NS, 2>), dim3(grid), dim3(512), lds_s, s, a);
+        CDF_LAUNCH_LDS((conv_igemm_rowhalo_stream_kernel<W, BN, NS, 2>), dim3(grid), dim3(512), L::bytes, s, a);
     else
-        CDF_LAUNCH((conv_igemm_rowhalo_stream_kernel<W, BN, NS, 4>), dim3(grid), dim3(512), lds_s, s, a);
+        CDF_LAUNCH_LDS((conv_igemm_rowhalo_stream_kernel<W, BN, NS, 4>), dim3(grid), dim3(512), L::bytes, s, a);
     return cdf_check_launch("conv_igemm_rowhalo_stream");
 }
 

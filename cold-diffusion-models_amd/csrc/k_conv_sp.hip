@@ -126,12 +126,7 @@ __global__ void __launch_bounds__(256, 2) conv_igemm_sp_kernel(SpArgs a) {
     };
 
     f32x16_t acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    cdf_acc_zero(acc);
 
     const int half = lane >> 5, l31 = lane & 31;
     if (niter > 0) {
@@ -283,12 +278,7 @@ __global__ void __launch_bounds__(256, 2) conv_wgrad_sp_kernel(SpWgradArgs a) {
     };
 
     f32x16_t acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    cdf_acc_zero(acc);
 
     const int half = lane >> 5, l31 = lane & 31;
     if (niter > 0) {
@@ -346,7 +336,7 @@ __global__ void __launch_bounds__(256, 2) conv_wgrad_sp_kernel(SpWgradArgs a) {
     for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int row = tile_a * BC + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+            const int row = tile_a * BC + wm * 64 + i * 32 + cdf_acc_row(r, half);
             if (row >= a.CA) continue;
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
@@ -487,19 +477,13 @@ __global__ void __launch_bounds__(512, 1) linattn_kvctx_kernel(KvCtxArgs a) {
     const bool ctx_wave = wave < 4;
     const int ch = wave & 3;
     f32x16_t cacc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) cacc[r] = 0.f;
+    cdf_acc_zero(cacc);
     float m_run = -3.0e38f, psum = 0.f;                      // lane (i = l31): column d = i of this head (both pixel parities hold m_run)
 
     if (t_lo < t_hi) load_chunk(t_lo, 0);
     for (int tile = t_lo; tile < t_hi; ++tile) {
         f32x16_t acc[2][2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+        cdf_acc_zero(acc);
         for (int c = 0; c < nch; ++c) {
             if (c > 0) __syncthreads();                       // every wave is done with the previous chunk's fragments
             store_lds();
@@ -540,13 +524,7 @@ __global__ void __launch_bounds__(512, 1) linattn_kvctx_kernel(KvCtxArgs a) {
         __syncthreads();                                      // the operand stage is free: it becomes the staging tile
         // ---- accumulators -> staging tile [pixel][channel]; the k waves (channel quarters 0, 1) leave the column maxima of their
         //      64 pixels next to it
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    stg[(wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * half) * SP + wn * 64 + j * 32 + l31] = acc[i][j][r];
+        cdf_acc_stage(stg, SP, wm * 64, wn * 64, acc, half, l31);
         if (wn < 2) {
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
@@ -574,9 +552,9 @@ __global__ void __launch_bounds__(512, 1) linattn_kvctx_kernel(KvCtxArgs a) {
             const float* vcol = kcol + HD;
             const float m_new = fmaxf(m_run, fmaxf(sstat[ch * LD + l31], sstat[HD + ch * LD + l31]));
             const float f = expf(m_run - m_new);                                       // (first tile: exp(-inf) = 0 on zero accumulators)
-            // accumulator row of register r is d = (r & 3) + 8 (r >> 2) + 4 half: its factor lives in lane d
+            // the factor of accumulator row d lives in lane d
 #pragma unroll
-            for (int r = 0; r < 16; ++r) cacc[r] *= __shfl(f, (r & 3) + 8 * (r >> 2) + 4 * half);
+            for (int r = 0; r < 16; ++r) cacc[r] *= __shfl(f, cdf_acc_row(r, half));
             psum *= f;
             m_run = m_new;
 #pragma unroll 8
@@ -592,8 +570,7 @@ __global__ void __launch_bounds__(512, 1) linattn_kvctx_kernel(KvCtxArgs a) {
     psum += __shfl_xor(psum, 32);
     float* fold = stg;                                        // [4 heads][32][32], then [4][32] sums
     if (ctx_wave) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) fold[(ch * LD + (r & 3) + 8 * (r >> 2) + 4 * half) * LD + l31] = cacc[r];
+        cdf_acc_stage(fold, LD, ch * LD, 0, cacc, half, l31);
         if (half == 0) fold[4 * LD * LD + ch * LD + l31] = psum;
     }
     __syncthreads();
@@ -646,21 +623,12 @@ extern "C" int cdf_linattn_kvctx(const float* xn, int ldx, const void* w_hi, con
     a.ldx = ldx; a.ldk = ldk; a.ldkv = ldkv; a.n = n; a.dim = dim; a.P = P;
     a.tiles_per_block = (tiles + P - 1) / P;
     const size_t lds = (size_t)128 * (256 + 8) * sizeof(float) + 8 * 32 * sizeof(float);
-#ifndef CDF_EMU
-    static CdfDeviceLatch attr_done;
-    if (attr_done.first()) {
-        (void)hipFuncSetAttribute((const void*)linattn_kvctx_kernel<1, 32>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)linattn_kvctx_kernel<3, 32>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)linattn_kvctx_kernel<1, 64>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)linattn_kvctx_kernel<3, 64>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    }
-#endif
     if (dim % 64 == 0) {
-        if (w_lo) CDF_LAUNCH((linattn_kvctx_kernel<3, 64>), dim3(P, B), dim3(512), lds, CDF_S, a);
-        else CDF_LAUNCH((linattn_kvctx_kernel<1, 64>), dim3(P, B), dim3(512), lds, CDF_S, a);
+        if (w_lo) CDF_LAUNCH_LDS((linattn_kvctx_kernel<3, 64>), dim3(P, B), dim3(512), lds, CDF_S, a);
+        else CDF_LAUNCH_LDS((linattn_kvctx_kernel<1, 64>), dim3(P, B), dim3(512), lds, CDF_S, a);
     } else {
-        if (w_lo) CDF_LAUNCH((linattn_kvctx_kernel<3, 32>), dim3(P, B), dim3(512), lds, CDF_S, a);
-        else CDF_LAUNCH((linattn_kvctx_kernel<1, 32>), dim3(P, B), dim3(512), lds, CDF_S, a);
+        if (w_lo) CDF_LAUNCH_LDS((linattn_kvctx_kernel<3, 32>), dim3(P, B), dim3(512), lds, CDF_S, a);
+        else CDF_LAUNCH_LDS((linattn_kvctx_kernel<1, 32>), dim3(P, B), dim3(512), lds, CDF_S, a);
     }
     return cdf_check_launch("linattn_kvctx");
 }
@@ -707,19 +675,12 @@ extern "C" int cdf_conv_gemm_bf16(const float* x, int ldx, const void* w_hi, con
     }
     const int M = B * QH * QW;
     const int tiles = cdf_cdiv(M, 128) * cdf_cdiv(Cout, 128);
-#ifndef CDF_EMU
-    static CdfDeviceLatch attr_done;
-    if (attr_done.first()) {
-        (void)hipFuncSetAttribute((const void*)conv_igemm_sp_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)conv_igemm_sp_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    }
-#endif
     if (split == 1) {
         const size_t lds = CDF_SP_EPI_LDS;                 // operand stages (40 KB) < epilogue tile
-        CDF_LAUNCH((conv_igemm_sp_kernel<1>), dim3(tiles, nphase), dim3(256), lds, CDF_S, a);
+        CDF_LAUNCH_LDS((conv_igemm_sp_kernel<1>), dim3(tiles, nphase), dim3(256), lds, CDF_S, a);
     } else {
         const size_t lds = (size_t)2 * 2 * 2 * 128 * 40 * sizeof(unsigned short);   // 80 KB >= CDF_SP_EPI_LDS
-        CDF_LAUNCH((conv_igemm_sp_kernel<3>), dim3(tiles, nphase), dim3(256), lds, CDF_S, a);
+        CDF_LAUNCH_LDS((conv_igemm_sp_kernel<3>), dim3(tiles, nphase), dim3(256), lds, CDF_S, a);
     }
     return cdf_check_launch("conv_igemm_sp");
 }
@@ -742,15 +703,9 @@ extern "C" int cdf_conv_wgrad_bf16(const float* xa, int lda, const float* xb, in
         a.dby[t] = (signed char)tap_desc[4 * t + 2];
         a.dbx[t] = (signed char)tap_desc[4 * t + 3];
     }
-#ifndef CDF_EMU
-    static CdfDeviceLatch attr_done;
-    if (attr_done.first()) {
-        (void)hipFuncSetAttribute((const void*)conv_wgrad_sp_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    }
-#endif
     const size_t lds = (size_t)2 * 4 * 32 * 128 * sizeof(unsigned short);
     const int tiles = cdf_cdiv(CA, 128) * cdf_cdiv(CB, 128);
-    CDF_LAUNCH(conv_wgrad_sp_kernel, dim3(tiles, ntaps, nsplit), dim3(256), lds, CDF_S, a);
+    CDF_LAUNCH_LDS(conv_wgrad_sp_kernel, dim3(tiles, ntaps, nsplit), dim3(256), lds, CDF_S, a);
     return cdf_check_launch("conv_wgrad_sp");
 }
 

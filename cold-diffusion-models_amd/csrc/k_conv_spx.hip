@@ -15,12 +15,12 @@ __global__ void __launch_bounds__(64 * WM * WN, OCC) conv_igemm_spx_kernel(SpxAr
     // c ^ ((r >> 2) & 3) -- the lane that fills LDS slot (r, c') fetches global column c' ^ ((r >> 2) & 3), the
     // fragment read of (r, c) goes to c ^ ((r >> 2) & 3).  With that the 16 rows of every ds_read_b128 lane group
     // (rows = r mod 4 classes x 4 distinct (r >> 2) & 3) cover all 64 banks exactly once.
-    constexpr int BK = 32, RE = 32, NW = WM * WN, NTHR = 64 * NW;     // RE: row elements (64 bytes)
+    constexpr int BK = 32, RE = CDF_SP_RE, NW = WM * WN;              // RE: row elements (64 bytes)
     constexpr int MT = BM / WM / 32, NT = BN / WN / 32;               // 32 x 32 MFMA tiles per wave
     constexpr int SA = BM / 16 / NW, SB = BN / 16 / NW;               // 16-row DMA segments per wave and plane
     static_assert(SA >= 1 && SB >= 1 && SA * NW * 16 == BM && SB * NW * 16 == BN, "tile must split into 16-row segments per wave");
-    constexpr int PLANE_A = BM * RE, PLANE_B = BN * RE;
-    constexpr int STAGE = 2 * PLANE_A + 2 * PLANE_B;                  // A hi, A lo, B hi, B lo
+    using L = SpxLayout<BM, BN, NSTAGE>;
+    constexpr int PLANE_A = L::PLANE_A, PLANE_B = L::PLANE_B, STAGE = L::STAGE;   // a stage: A hi, A lo, B hi, B lo
     CDF_DYN_SMEM(smem_raw);
     unsigned short* smem = (unsigned short*)smem_raw;
 
@@ -34,8 +34,7 @@ __global__ void __launch_bounds__(64 * WM * WN, OCC) conv_igemm_spx_kernel(SpxAr
 
     // DMA slots of this lane: wave w fills the 16-row segments w*SA + p of both A planes and w*SB + p of both B planes;
     // inside a segment lane l is row l >> 2, LDS column l & 3, i.e. global column (l & 3) ^ ((l >> 4) & 3).
-    const int srow = lane >> 2;
-    const int q8 = ((lane & 3) ^ ((lane >> 4) & 3)) * 8;
+    const int srow = cdf_dma_row(lane), q8 = cdf_dma_col(lane);
     int a_iy0[SA], a_ix0[SA], b_row[SB];
     unsigned a_pix[SA];
 #pragma unroll
@@ -54,8 +53,7 @@ __global__ void __launch_bounds__(64 * WM * WN, OCC) conv_igemm_spx_kernel(SpxAr
     }
 #pragma unroll
     for (int p = 0; p < SB; ++p) {
-        const int n = tile_n * BN + (wave * SB + p) * 16 + srow;
-        b_row[p] = n < a.Cout ? n : a.Cout - 1;
+        b_row[p] = cdf_w_row(tile_n * BN + (wave * SB + p) * 16 + srow, a.Cout);
     }
     const int nchunks = (a.Cin + BK - 1) / BK;
     // split-K over the taps (small grids: see dispatch_gemm_bf16x): this block's share of the taps
@@ -72,7 +70,7 @@ __global__ void __launch_bounds__(64 * WM * WN, OCC) conv_igemm_spx_kernel(SpxAr
     // the 4 MB L2 per third, each of the three reads came over the fabric (measured 3.4x the algorithmic bytes).  Here tile j
     // handles group dy in slot (j + dy) mod 3: the tiles of an XCD run in lockstep (same start, same work), so the three
     // readers of a row now read it at the same time and the L2 fetches it once.
-    int* tap_lds = (int*)(smem + NSTAGE * STAGE);
+    int* tap_lds = (int*)(smem + L::OFF_TAPS);
     if (tid <= CDF_MAX_TAPS) {
         int src = tid + tap_lo;
         if (src > CDF_MAX_TAPS) src = CDF_MAX_TAPS;
@@ -113,7 +111,7 @@ __global__ void __launch_bounds__(64 * WM * WN, OCC) conv_igemm_spx_kernel(SpxAr
         }
 #pragma unroll
         for (int p = 0; p < SB; ++p) {
-            const size_t woff = (size_t)((unsigned)wi * (unsigned)a.Cout + (unsigned)b_row[p]) * (unsigned)a.ldk + (unsigned)q8;
+            const size_t woff = cdf_w_off(wi, a.Cout, b_row[p], a.ldk, q8);
             pb_hi[p] = a.w_hi + woff;
             pb_lo[p] = a.w_lo + woff;
         }
@@ -132,7 +130,7 @@ __global__ void __launch_bounds__(64 * WM * WN, OCC) conv_igemm_spx_kernel(SpxAr
         }
 #pragma unroll
         for (int p = 0; p < SB; ++p) {
-            unsigned short* seg = st + 2 * PLANE_A + (wave * SB + p) * 16 * RE;
+            unsigned short* seg = st + L::OFF_B + (wave * SB + p) * 16 * RE;
             CDF_GLDS16(pb_hi[p], seg);                       // (weights are zero padded along K to the chunk size)
             if constexpr (NS == 3) CDF_GLDS16(pb_lo[p], seg + PLANE_B);
         }
@@ -160,12 +158,7 @@ __global__ void __launch_bounds__(64 * WM * WN, OCC) conv_igemm_spx_kernel(SpxAr
     };
 
     f32x16_t acc[MT][NT];
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < NT; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    cdf_acc_zero(acc);
 
     const int half = lane >> 5, l31 = lane & 31;
     const int sw = (l31 >> 2) & 3;                           // read-side swizzle (tile row offsets are multiples of 32)
@@ -183,58 +176,26 @@ __global__ void __launch_bounds__(64 * WM * WN, OCC) conv_igemm_spx_kernel(SpxAr
     CDF_LDS_BARRIER();
     int buf = 0;
     bf16x8_v ah[2][MT], al[2][MT], bh[2][NT], bl[2][NT];
-    // De-phased waves (a.dephase, 8-wave tiles: waves 4..7 share their SIMDs with waves 0..3): a late wave multiplies the
-    // fragments it read in the PREVIOUS step first, then issues its DMA and reads this step's fragments -- while one wave of a
-    // SIMD is stalled issuing global_load_lds / reading LDS the other one feeds the matrix pipe (see conv_igemm_halo_kernel).
+    // De-phased waves (cdf_dephased_step; 8-wave tiles only): a late wave also issues its DMA after its MFMAs
     const bool late = a.dephase != 0 && NW == 8 && wave >= 4;    // (wave-uniform)
-    if (late) {
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-#pragma unroll
-            for (int i = 0; i < MT; ++i)
-#pragma unroll
-                for (int e = 0; e < 8; ++e) { ah[ks][i][e] = 0; al[ks][i][e] = 0; }
-#pragma unroll
-            for (int j = 0; j < NT; ++j)
-#pragma unroll
-                for (int e = 0; e < 8; ++e) { bh[ks][j][e] = 0; bl[ks][j][e] = 0; }
-        }
-    }
-    auto read_frags = [&](const unsigned short* sa, const unsigned short* sb) {
+    if (late) cdf_frag_zero(ah, al, bh, bl);
+    auto fetch_read = [&]() {
+        fetch(fbuf);                                         // chunk it + NSTAGE - 1
+        fbuf = fbuf + 1 == NSTAGE ? 0 : fbuf + 1;
+        const unsigned short* sa = smem + buf * STAGE;
+        const unsigned short* sb = sa + L::OFF_B;
+        buf = buf + 1 == NSTAGE ? 0 : buf + 1;
         // all fragment reads of the chunk are issued up front: the second k-step's LDS latency hides behind the first
         // k-step's MFMAs (the registers are there -- LDS, not VGPRs, limits the residency)
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
-            const int kc = ((ks * 2 + half) ^ sw) * 8;
-#pragma unroll
-            for (int i = 0; i < MT; ++i) {
-                const int off = (wm * (BM / WM) + i * 32 + l31) * RE + kc;
-                ah[ks][i] = *(const bf16x8_v*)(sa + off);
-                if constexpr (NS == 3) al[ks][i] = *(const bf16x8_v*)(sa + PLANE_A + off);
-            }
-#pragma unroll
-            for (int j = 0; j < NT; ++j) {
-                const int off = (wn * (BN / WN) + j * 32 + l31) * RE + kc;
-                bh[ks][j] = *(const bf16x8_v*)(sb + off);
-                if constexpr (NS == 3) bl[ks][j] = *(const bf16x8_v*)(sb + PLANE_B + off);
-            }
+            cdf_read_frags<NS, PLANE_A>(ah[ks], al[ks], sa, ks, half, wm * (BM / WM) + l31, sw);
+            cdf_read_frags<NS, PLANE_B>(bh[ks], bl[ks], sb, ks, half, wn * (BN / WN) + l31, sw);
         }
     };
-    auto mma_frags = [&]() {
-        cdf_mma_tile<NS, MT, NT>(acc, ah, al, bh, bl);
-    };
+    auto mma_frags = [&]() { cdf_mma_tile<NS, MT, NT>(acc, ah, al, bh, bl); };
     for (int it = 0; it < niter; ++it) {
-        if (late) {
-            mma_frags();
-            CDF_SCHED_FENCE();
-        }
-        fetch(fbuf);                                         // chunk it + NSTAGE - 1
-        fbuf = fbuf + 1 == NSTAGE ? 0 : fbuf + 1;
-        const unsigned short* sa = smem + buf * STAGE;
-        const unsigned short* sb = sa + 2 * PLANE_A;
-        buf = buf + 1 == NSTAGE ? 0 : buf + 1;
-        read_frags(sa, sb);
-        if (!late) mma_frags();
+        cdf_dephased_step(late, fetch_read, mma_frags);
         CDF_WAIT_DMA_LEAVE((NSTAGE - 2) * PIECES);           // this wave's pieces of chunk it + 1 have landed ...
         CDF_LDS_BARRIER();                                   // ... and so have everybody else's; chunk it is fully consumed
     }
@@ -248,16 +209,8 @@ __global__ void __launch_bounds__(64 * WM * WN, OCC) conv_igemm_spx_kernel(SpxAr
         r.Cout = a.Cout; r.vec = (a.Cout & 3) == 0 ? 1 : 0; r.os = 1; r.QH = 1; r.QW = 1; r.OH = 1; r.OW = 1; r.ldy = a.ks_ld;
         r.ldp = r.ldm = r.ldr = r.ld_sbias = r.ld_ys = 0; r.act = 0; r.mul_mode = 0; r.accumulate = 0;
         r.bias = nullptr; r.sbias = nullptr; r.pre = nullptr; r.mul = nullptr; r.res = nullptr; r.ys_hi = nullptr; r.ys_lo = nullptr; r.io_bf = 0;
-        constexpr int CP = BN + 8, TM = BM / WM, TN = BN / WN;
         float* cs = (float*)smem_raw;
-        const int half_ = lane >> 5, l31_ = lane & 31;
-#pragma unroll
-        for (int i = 0; i < TM / 32; ++i)
-#pragma unroll
-            for (int j = 0; j < TN / 32; ++j)
-#pragma unroll
-                for (int rr = 0; rr < 16; ++rr)
-                    cs[(wm * TM + i * 32 + (rr & 3) + 8 * (rr >> 2) + 4 * half_) * CP + wn * TN + j * 32 + l31_] = acc[i][j][rr];
+        cdf_acc_stage(cs, BN + 8, wm * (BM / WM), wn * (BN / WN), acc, half, l31);
         __syncthreads();
         cdf_epilogue_rows<BN, BM, 64 * WM * WN>(r, ph, a.ks_ws + (size_t)blockIdx.z * M * a.ks_ld, cs, tile_m * BM, tile_n * BN, M, tid,
                                                 [](int p) { return p; });
@@ -319,20 +272,10 @@ extern "C" int cdf_gemm_tuning_default(cdf_gemm_tuning* t) {
 
 template <int NS, int BM, int BN, int WM, int WN, int NSTAGE, int OCC = 512 / (64 * WM * WN)>
 static int launch_igemm_spx(const SpxArgs& a, int M, hipStream_t s, CdfPlan* plan) {
-    constexpr size_t stages = (size_t)NSTAGE * 2 * (BM + BN) * 32 * sizeof(unsigned short) + (CDF_MAX_TAPS + 1) * sizeof(int);
-    constexpr size_t epi = (size_t)BM * (BN + 8) * sizeof(float);
-    constexpr size_t lds = stages > epi ? stages : epi;      // 128 x 128 x 2 stages: 68 KB (epilogue tile), two blocks per CU;
-                                                             // 256 x 128 x 3 stages: 144 KB, one block per CU
-    static_assert(lds <= 160 * 1024, "tile does not fit the LDS");
+    using L = SpxLayout<BM, BN, NSTAGE>;
     const int tiles = cdf_cdiv(M, BM) * cdf_cdiv(a.Cout, BN);
     if (plan) return cdf_plan_set(plan, CDF_FORM_SPX, BM, BN, NSTAGE, a.ksplit > 1 ? a.ksplit : 1, 0, tiles, (long long)tiles * a.nphase * (a.ksplit > 1 ? a.ksplit : 1));
-#ifndef CDF_EMU
-    static CdfDeviceLatch attr_done;
-    if (attr_done.first()) {
-        (void)hipFuncSetAttribute((const void*)conv_igemm_spx_kernel<BM, BN, WM, WN, NSTAGE, OCC, NS>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    }
-#endif
-    CDF_LAUNCH((conv_igemm_spx_kernel<BM, BN, WM, WN, NSTAGE, OCC, NS>), dim3(tiles, a.nphase, a.ksplit > 1 ? a.ksplit : 1), dim3(64 * WM * WN), lds, s, a);
+    CDF_LAUNCH_LDS((conv_igemm_spx_kernel<BM, BN, WM, WN, NSTAGE, OCC, NS>), dim3(tiles, a.nphase, a.ksplit > 1 ? a.ksplit : 1), dim3(64 * WM * WN), L::bytes, s, a);
     if (a.ksplit > 1) {
         const int ftiles = cdf_cdiv(M, 16) * cdf_cdiv(a.Cout, BN);
         if (BN == 64) CDF_LAUNCH((conv_splitk_finish_kernel<64>), dim3(ftiles), dim3(256), 0, s, a);

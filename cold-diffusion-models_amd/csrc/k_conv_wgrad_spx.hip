@@ -150,12 +150,7 @@ __global__ void __launch_bounds__(256, 2) conv_wgrad_spx_kernel(SpxWgradArgs a) 
     };
 
     f32x16_t acc[MT][NT];
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < NT; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    cdf_acc_zero(acc);
 
     const int half = lane >> 5, l31 = lane & 31;
     // transposing-read lane geometry: group g = lane >> 4 -> channel block 16 (g & 1), pixel block 8 (g >> 1)
@@ -224,13 +219,7 @@ __global__ void __launch_bounds__(256, 2) conv_wgrad_spx_kernel(SpxWgradArgs a) 
     }
     // accumulators -> LDS [TA][TB + 8] -> float4 rows of the split's partial-sum slab (see cdf_epilogue.h)
     constexpr int CP = TB + 8;
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < NT; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r)
-                red[(wm * (TA / 2) + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * half) * CP + wn * (TB / 2) + j * 32 + l31] = acc[i][j][r];
+    cdf_acc_stage(red, CP, wm * (TA / 2), wn * (TB / 2), acc, half, l31);
     __syncthreads();
     float* O = a.out + ((long long)split * a.ntaps + tap) * a.CA * a.ldo;
     constexpr int TPR = TB / 4, RPS = 256 / TPR;
@@ -370,12 +359,7 @@ __global__ void __launch_bounds__(512, 1) conv_wgrad_row3_kernel(SpxWgradArgs a)
     };
 
     f32x16_t acc[3][NT];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < NT; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    cdf_acc_zero(acc);
 
     const int half = lane >> 5, l31 = lane & 31;
     const int t16 = lane & 15, g16 = lane >> 4;
@@ -474,11 +458,7 @@ __global__ void __launch_bounds__(512, 1) conv_wgrad_row3_kernel(SpxWgradArgs a)
     const int c4 = (tid % TPR) * 4, col = tile_b * TB + c4;
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
-#pragma unroll
-        for (int j = 0; j < NT; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r)
-                red[(wa * 32 + (r & 3) + 8 * (r >> 2) + 4 * half) * CP + wb * TNW + j * 32 + l31] = acc[i][j][r];
+        cdf_acc_stage(red, CP, wa * 32, wb * TNW, acc[i], half, l31);
         __syncthreads();
         float* O = a.out + ((long long)split * a.ntaps + 3 * grp + i) * a.CA * a.ldo;
         if (col < a.ldo) {
@@ -506,13 +486,7 @@ static int launch_wgrad_spx(const SpxWgradArgs& a, hipStream_t s, CdfPlan* plan)
     constexpr size_t lds = 2 * stage > epi ? 2 * stage : epi;
     const int tiles = (STACK2 ? 1 : cdf_cdiv(a.CA, TA)) * cdf_cdiv(a.CB, TB);
     if (plan) return cdf_plan_set(plan, STACK2 ? CDF_FORM_WGRAD_STACK2 : CDF_FORM_WGRAD_SPX, TA, TB, 0, 0, 0, tiles, (long long)tiles * (STACK2 ? cdf_cdiv(a.ntaps, 2) : a.ntaps) * a.nsplit);
-#ifndef CDF_EMU
-    static CdfDeviceLatch attr_done;
-    if (attr_done.first()) {
-        (void)hipFuncSetAttribute((const void*)conv_wgrad_spx_kernel<TA, TB, STACK2, NS>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    }
-#endif
-    CDF_LAUNCH((conv_wgrad_spx_kernel<TA, TB, STACK2, NS>), dim3(tiles, STACK2 ? cdf_cdiv(a.ntaps, 2) : a.ntaps, a.nsplit), dim3(256), lds, s, a);
+    CDF_LAUNCH_LDS((conv_wgrad_spx_kernel<TA, TB, STACK2, NS>), dim3(tiles, STACK2 ? cdf_cdiv(a.ntaps, 2) : a.ntaps, a.nsplit), dim3(256), lds, s, a);
     return cdf_check_launch("conv_wgrad_spx");
 }
 
@@ -530,13 +504,7 @@ static int launch_wgrad_row3(const SpxWgradArgs& a, hipStream_t s, CdfPlan* plan
     constexpr size_t lds = 2 * stage > epi ? 2 * stage : epi;
     const int tiles = cdf_cdiv(a.CA, TA) * cdf_cdiv(a.CB, TB);
     if (plan) return cdf_plan_set(plan, CDF_FORM_WGRAD_ROW3, TA, TB, 0, 0, 0, tiles, (long long)tiles * 3 * a.nsplit);
-#ifndef CDF_EMU
-    static CdfDeviceLatch attr_done;
-    if (attr_done.first()) {
-        (void)hipFuncSetAttribute((const void*)conv_wgrad_row3_kernel<TA, TB, NS>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    }
-#endif
-    CDF_LAUNCH((conv_wgrad_row3_kernel<TA, TB, NS>), dim3(tiles, 3, a.nsplit), dim3(512), lds, s, a);
+    CDF_LAUNCH_LDS((conv_wgrad_row3_kernel<TA, TB, NS>), dim3(tiles, 3, a.nsplit), dim3(512), lds, s, a);
     return cdf_check_launch("conv_wgrad_row3");
 }
 

@@ -740,7 +740,7 @@ static inline int ew_grid(long long n, int block) {
 
 template <int K, int SW>
 static int launch_blur_plane(const BlurArgs& a, int nt, size_t lds, hipStream_t s) {
-    CDF_LAUNCH((blur_plane_lds_kernel<K, SW>), dim3(a.B * a.C), dim3(nt), lds, s, a);
+    CDF_LAUNCH_LDS((blur_plane_lds_kernel<K, SW>), dim3(a.B * a.C), dim3(nt), lds, s, a);
     return cdf_check_launch("blur_plane_lds");
 }
 
@@ -765,16 +765,6 @@ extern "C" int cdf_blur_chain(const float* x, float* y, float* snap, const float
     int nt = ((nstrips + 63) / 64) * 64;
     if (nt > 1024) nt = 1024;
     if (nt < 64) nt = 64;
-#ifndef CDF_EMU
-    static CdfDeviceLatch attr_done;
-    if (attr_done.first()) {
-        // allow > 64 KB dynamic LDS for every instantiation
-#define CDF_SET_LDS(K, SW) (void)hipFuncSetAttribute((const void*)blur_plane_lds_kernel<K, SW>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)
-        CDF_SET_LDS(3, 8); CDF_SET_LDS(11, 8); CDF_SET_LDS(15, 8); CDF_SET_LDS(27, 8); CDF_SET_LDS(0, 8);
-        CDF_SET_LDS(3, 4); CDF_SET_LDS(11, 4); CDF_SET_LDS(15, 4); CDF_SET_LDS(27, 4); CDF_SET_LDS(0, 4);
-#undef CDF_SET_LDS
-    }
-#endif
 #define CDF_BLUR_CASE(K)                                                      \
     case K:                                                                   \
         return sw8 ? launch_blur_plane<K, 8>(a, nt, lds, CDF_S) : launch_blur_plane<K, 4>(a, nt, lds, CDF_S);
@@ -791,13 +781,7 @@ extern "C" int cdf_blur_chain(const float* x, float* y, float* snap, const float
 
 template <int K>
 static int launch_blur_sep(const BlurArgs& a, int nt, size_t lds, hipStream_t s) {
-#ifndef CDF_EMU
-    static CdfDeviceLatch attr_done;
-    if (attr_done.first()) {
-        (void)hipFuncSetAttribute((const void*)blur_plane_sep_kernel<K>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    }
-#endif
-    CDF_LAUNCH((blur_plane_sep_kernel<K>), dim3(a.B * a.C), dim3(nt), lds, s, a);
+    CDF_LAUNCH_LDS((blur_plane_sep_kernel<K>), dim3(a.B * a.C), dim3(nt), lds, s, a);
     return cdf_check_launch("blur_plane_sep");
 }
 
@@ -864,13 +848,7 @@ extern "C" int cdf_pixelate_chain(const float* x, float* y, float* snap, const f
     CDF_REQUIRE(lds <= 160 * 1024, "cdf_pixelate_chain: %dx%d plane does not fit LDS", H, H);
     PixArgs a{x, y, snap, img, sizes, t, B, C, H, step_lo, step_hi, mode};
     int nt = H * H >= 4096 ? 1024 : 256;
-#ifndef CDF_EMU
-    static CdfDeviceLatch attr_done;
-    if (attr_done.first()) {
-        (void)hipFuncSetAttribute((const void*)pixelate_plane_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    }
-#endif
-    CDF_LAUNCH(pixelate_plane_kernel, dim3(B * C), dim3(nt), lds, CDF_S, a);
+    CDF_LAUNCH_LDS(pixelate_plane_kernel, dim3(B * C), dim3(nt), lds, CDF_S, a);
     return cdf_check_launch("pixelate_plane");
 }
 

@@ -560,14 +560,8 @@ static int launch_dwconv7(const void* x, int ldx, const float* w, int ldw, const
                           int ldy, int B, int H, int W, int C4, int flip, int accumulate, const void* res, int ldr, hipStream_t s,
                           void* y_hi = nullptr, void* y_lo = nullptr, int ld_ys = 0) {
     constexpr size_t lds = ((size_t)(TBH + 6) * ((TBW + 6) * 8 + 4) + DW_TAPS * 8) * sizeof(float4);
-#ifndef CDF_EMU
-    static CdfDeviceLatch attr_done;
-    if (attr_done.first()) {
-        (void)hipFuncSetAttribute((const void*)dwconv7_kernel<TBW, TBH, BF, YB>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    }
-#endif
     const long long tiles = (long long)B * cdf_cdiv(H, TBH) * cdf_cdiv(W, TBW);
-    CDF_LAUNCH((dwconv7_kernel<TBW, TBH, BF, YB>), dim3((unsigned)tiles, cdf_cdiv(C4, 8)), dim3(256), lds, s, x, ldx, w, ldw, bias, sbias, ld_sbias, y,
+    CDF_LAUNCH_LDS((dwconv7_kernel<TBW, TBH, BF, YB>), dim3((unsigned)tiles, cdf_cdiv(C4, 8)), dim3(256), lds, s, x, ldx, w, ldw, bias, sbias, ld_sbias, y,
                ldy, B, H, W, C4, flip, accumulate, res, ldr, y_hi, y_lo, ld_ys);
     return cdf_check_launch("dwconv7");
 }

@@ -539,17 +539,7 @@ static int ln_bwd_launch(const void* dy, int lddy, const void* x, int ldx, const
     const int nb = cdf_layernorm_blocks(M, C);
     const int G = 4 * (64 / LP);
     const size_t lds = (size_t)G * 2 * C * sizeof(float);
-#ifndef CDF_EMU
-    static CdfDeviceLatch attr_done;
-    if (attr_done.first()) {
-#define CDF_LN_ATTR(N, IO) (void)hipFuncSetAttribute((const void*)layernorm_c_bwd_kernel<N, IO>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)
-        CDF_LN_ATTR(1, 0); CDF_LN_ATTR(2, 0); CDF_LN_ATTR(3, 0); CDF_LN_ATTR(4, 0);
-        CDF_LN_ATTR(1, 7); CDF_LN_ATTR(2, 7); CDF_LN_ATTR(3, 7); CDF_LN_ATTR(4, 7);
-        CDF_LN_ATTR(1, 14); CDF_LN_ATTR(2, 14); CDF_LN_ATTR(3, 14); CDF_LN_ATTR(4, 14);
-#undef CDF_LN_ATTR
-    }
-#endif
-#define CDF_LN_BWD(N, IO) CDF_LAUNCH((layernorm_c_bwd_kernel<N, IO>), dim3(nb), dim3(256), lds, CDF_S, dy, lddy, x, ldx, g, mean, rstd, dx, lddx, part, M, C, LP, add, ldadd, (unsigned short*)dx_hi, (unsigned short*)dx_lo, ld_planes)
+#define CDF_LN_BWD(N, IO) CDF_LAUNCH_LDS((layernorm_c_bwd_kernel<N, IO>), dim3(nb), dim3(256), lds, CDF_S, dy, lddy, x, ldx, g, mean, rstd, dx, lddx, part, M, C, LP, add, ldadd, (unsigned short*)dx_hi, (unsigned short*)dx_lo, ld_planes)
 #define CDF_LN_BWD_NV(IO)                  \
     switch (NV) {                          \
         case 1: CDF_LN_BWD(1, IO); break;  \

@@ -23,7 +23,7 @@ constants (|GELU'| <= 1.13, |SiLU'| <= 1.1, |GELU''| <= 0.8) and add the documen
 7.1.26: 1.5e-7 absolute, csrc/cdf_common.h) -- see _epilogue64.  Second assertion, unchanged from test_kernels.py::_spx_case: the
 distance to the TRUE float64 convolution of the unsplit operands stays within 3e-5 max(1, |ref|max) (2e-2 for NS = 1).
 
-K_SUM stays 4 for the GEMMs.  Worst error / bound over all cases of this module on the MI355X (135 GPU cases, 72 s):
+K_SUM stays 4 for the GEMMs.  Worst error / bound over all cases of this module on the MI355X (144 GPU cases):
     GEMM outputs                y 0.41 (NS = 3), 0.29 (NS = 1);   pre-activation / GELU' output 0.37, 0.55 (bf16 storage)
     GEMM output planes          hi + lo 0.29;   hi only 0.87 (the bound there is bf16's own half ulp, 2^-8 |v|)
     true float64 convolution    0.26 of 3e-5 max (NS = 3), 0.20 of 2e-2 max (NS = 1)
@@ -671,6 +671,26 @@ def test_gemm_bench_forms(row):
         _, tiles, grid = gemm_form(be.L, row, be.tune.ptr)
         assert tiles > grid, "the resident kernel's rows must walk several tiles per block"
         _gemm_case(be, row, tune=dict(resident_reserve=32))
+
+
+# Kernel instantiations of the device build that neither a recording (BENCH_GEMM) nor another hardware test launches (kernel trace of this
+# module, test_kernels.py and test_kernels_production.py against the build's instantiation list): (row, tuning, (form, bm, bn, stages)), at the
+# smallest batch that dispatches there -- width and channel counts are template parameters.  The resident kernel's rows take B = 5: 320 tiles
+# on 256 blocks, an uneven walk.  Its 64-wide N tile is reached through cdf_gemm_tuning.halo bit 64 only.
+UNRECORDED_GEMM = [
+    *[(("gemm", "conv_fwd", 5, 128, 128, 128, 128, 3, 1, 1, 1, "b", 0, 0, 0, 0, 0, 1, 0, ns), None, (ROWHALO, 256, 128, 4)) for ns in (1, 3)],
+    *[(("gemm", "conv_fwd", 5, 128, 128, cin, 64, 3, 1, 1, 1, "b", 0, 0, 0, 0, 0, 1, 0, ns), dict(halo=64 | 47), (ROWHALO, 256, 64, cin // 32))
+      for cin in (64, 128) for ns in (1, 3)],
+    *[(("gemm", "conv_fwd", 2, 128, 128, 64, 64, 1, 1, 0, 1, "b", 0, 0, 0, 0, 0, 1, 0, ns), None, (SPX, 64, 64, 2)) for ns in (1, 3)],
+    (("gemm", "conv_fwd", 1, 32, 32, 64, 96, 3, 1, 1, 1, "b", 0, 0, 0, 0, 0, 1, 0, 1), None, (HALO, 128, 128, 6)),
+]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("row,tune,form", UNRECORDED_GEMM, ids=lambda v: "-".join(map(str, v)) if isinstance(v, tuple) else str(v))
+def test_gemm_instances_no_recording_reaches(row, tune, form):
+    d = decode(_gemm_case(_hip(), row, tune=dict(tune or {})))
+    assert (d["form"], d["bm"], d["bn"], d["stages"]) == form
 
 
 def test_bench_gemm_reaches_resident_blocks_with_several_tiles():

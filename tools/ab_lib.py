@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Build a SECOND library for same-call A/Bs: the current objects with some sources taken from another git revision.
+"""Build a SECOND library for same-call A/Bs: the current objects with some sources taken from another git revision, compiled against THAT
+revision's headers (csrc/*.h, include/colddiff.h) -- never a hybrid of old kernels and new helpers.
 
     python tools/ab_lib.py <rev> k_dwconv.hip [more.hip ...]   ->  tools/_ablate/ab/lib_prev.so
 
@@ -18,12 +19,18 @@ def main():
     rev, names = sys.argv[1], sys.argv[2:]
     out_dir = os.path.join(REPO, "tools", "_ablate", "ab")
     os.makedirs(out_dir, exist_ok=True)
-    flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wno-unused-result", "-I", CSRC, "-I", os.path.join(REPO, "include")]
+    show = lambda path: subprocess.run(["git", "-C", REPO, "show", f"{rev}:{path}"], capture_output=True, text=True, check=True).stdout
+    hdr_dir = os.path.join(out_dir, "headers_" + rev.replace("/", "_"))
+    os.makedirs(hdr_dir, exist_ok=True)
+    tree = subprocess.run(["git", "-C", REPO, "ls-tree", "--name-only", rev, "cold-diffusion-models_amd/csrc/", "include/colddiff.h"], capture_output=True, text=True, check=True).stdout.split()
+    for path in (t for t in tree if t.endswith(".h")):
+        open(os.path.join(hdr_dir, os.path.basename(path)), "w").write(show(path))
+    flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wno-unused-result", "-I", hdr_dir]
     objs = []
     for f in sorted(x for x in os.listdir(CSRC) if x.endswith(".hip")):
         if f in names:
             src = os.path.join(out_dir, f)
-            open(src, "w").write(subprocess.run(["git", "-C", REPO, "show", f"{rev}:cold-diffusion-models_amd/csrc/{f}"], capture_output=True, text=True, check=True).stdout)
+            open(src, "w").write(show(f"cold-diffusion-models_amd/csrc/{f}"))
             obj = os.path.join(out_dir, f[:-4] + ".o")
             subprocess.run([HIPCC] + flags + ["-c", src, "-o", obj], check=True)
             objs.append(obj)
