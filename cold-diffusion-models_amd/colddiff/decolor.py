@@ -480,9 +480,11 @@ def _square(image_size):
 
 class DecolorTrainer(Trainer):
     """diffusion.py:563-760 on the shared Trainer (fused gradient accumulation, flat Adam / EMA, device image cache).  The default dataset
-    chain is `CenterCrop(image_size)` on the file's own size; `to_lab=True` converts every batch with `cdf_lab_convert`; `random_aug` /
-    `torchvision_dataset` are torchvision's ColorJitter / RandomResizedCrop and its dataset classes: they run on the host `DataLoader`
-    when torchvision is importable and raise an ImportError naming the option otherwise."""
+    chain is `CenterCrop(image_size)` on the file's own size; `to_lab=True` converts every batch with `cdf_lab_convert`; `random_aug`
+    (RandomResizedCrop -> mirror -> RandomApply([ColorJitter])) runs on the device image cache in one launch per batch
+    (`cdf_augment_jitter_batch`, `trainer.RANDOM_AUG`) when `device_data` is on; with `device_data=False`, a folder the cache cannot hold,
+    or `torchvision_dataset` (torchvision's dataset classes) it is the host `DataLoader`, which needs torchvision and raises an
+    ImportError naming the option where that is missing."""
     image_size_from_model = False
     force_shuffle = True
 
@@ -504,8 +506,8 @@ class DecolorTrainer(Trainer):
         Path(results_folder).mkdir(parents=True, exist_ok=True)
         if image_size == 256 or (isinstance(image_size, (tuple, list)) and image_size[0] == 256):
             raise NotImplementedError("image_size 256 (CenterCrop(128) + Resize) is not built")
-        if random_aug or torchvision_dataset:
-            device_data = False
+        if torchvision_dataset:
+            device_data = False                     # (torchvision's dataset classes are host objects; `random_aug` alone runs on the device)
         super().__init__(diffusion_model, folder, ema_decay=ema_decay, image_size=_square(image_size), train_batch_size=train_batch_size,
                          train_lr=train_lr, train_num_steps=train_num_steps, gradient_accumulate_every=gradient_accumulate_every, fp16=fp16,
                          step_start_ema=step_start_ema, update_ema_every=update_ema_every, save_and_sample_every=save_and_sample_every,
@@ -516,6 +518,18 @@ class DecolorTrainer(Trainer):
     def _make_loader(self, folder, dataset, shuffle, num_workers, seed):
         if not (self.random_aug or self.torchvision_dataset):
             return super()._make_loader(folder, dataset, shuffle, num_workers, seed)
+        if self.random_aug and not self.torchvision_dataset and self.device_data and folder is not None and dataset != 'synthetic':
+            # the unresized RGB folder in HBM; RandomResizedCrop / mirror / ColorJitter / ToTensor per batch in one launch
+            from . import parallel
+            from .trainer import RANDOM_AUG, CacheUnfit, DeviceImageCache, DeviceLoader
+            self.recipe = RANDOM_AUG
+            try:
+                cache = DeviceImageCache(folder, self.data_image_size, self.device, recipe=RANDOM_AUG)
+                return cache, DeviceLoader(cache, self.batch_size, shuffle=True, seed=seed, rank=parallel.rank(), world=parallel.world_size(),
+                                           drop_last=self.drop_last or parallel.world_size() > 1)
+            except CacheUnfit as e:
+                print(f"device image cache not used ({e}); falling back to the host DataLoader")
+                self.device_data = False
         option = 'torchvision_dataset=True' if self.torchvision_dataset else 'random_aug=True'
         try:
             import torchvision                                                   # noqa: F401

@@ -61,13 +61,17 @@ class Recipe:
                                                                                        after an s x s crop returns its input)
     pad:    RandomCrop(s, padding=pad), constant fill 0                               (RESOL:825, DEFADE:588)
     crop:   'random' (RandomCrop) | 'center' (CenterCrop)
-    rgb:    img.convert('RGB') before the chain                                       (DENOISE:565, 588)"""
+    rgb:    img.convert('RGB') before the chain                                       (DENOISE:565, 588)
 
-    def __init__(self, name, resize, crop, flip, pad=0, rgb=False):
+    The one chain of another shape is crop 'rrc': RandomResizedCrop(s) -> mirror -> RandomApply([ColorJitter(*jitter)], p=jitter_p)
+    (decolorization / snowification `random_aug=True`, diffusion.py:516-526); its crop is resized PER SAMPLE, on the device."""
+
+    def __init__(self, name, resize, crop, flip, pad=0, rgb=False, jitter=None, jitter_p=0.0):
         self.name, self.resize, self.crop, self.flip, self.pad, self.rgb = name, resize, crop, flip, pad, rgb
+        self.jitter, self.jitter_p = jitter, jitter_p
 
     def with_rgb(self):
-        return Recipe(self.name, self.resize, self.crop, self.flip, self.pad, True)
+        return Recipe(self.name, self.resize, self.crop, self.flip, self.pad, True, self.jitter, self.jitter_p)
 
     def __repr__(self):
         return f"Recipe({self.name}: resize={self.resize} pad={self.pad} crop={self.crop} flip={self.flip} rgb={self.rgb})"
@@ -78,6 +82,7 @@ CENTER112 = Recipe('Dataset', 'sq112', 'center', False)                 # DEBLUR
 AUG2 = Recipe('Dataset_Aug2', 'short', 'random', True, pad=4)           # RESOL:817-831
 CIFAR_PAD = Recipe('DatasetCifar10', 'none', 'random', True, pad=4)     # DEFADE:579-599
 CENTER_SHORT = Recipe('Dataset', 'short', 'center', False)              # DEFADE:557-576
+RANDOM_AUG = Recipe('Dataset(random_aug)', 'none', 'rrc', True, jitter=(0.8, 0.8, 0.8, 0.2), jitter_p=0.8)   # DECOLOR diffusion.py:516-526
 
 
 def center_offset(full, size):
@@ -604,6 +609,83 @@ class CacheUnfit(Exception):
     budget): the Trainer falls back to the host Dataset + DataLoader."""
 
 
+JITTER_STRIDE = 16           # CDF_JITTER_STRIDE of include/colddiff.h: int32 words per image in the packed parameter table
+JITTER_LDS_CAP = 160 * 1024
+
+
+def jitter_lds_bytes(SH, SW, H, W):
+    """LDS need of cdf_augment_jitter_batch (csrc/k_data.hip, jitter_lds_bytes): the uint8 working image + the two coefficient tables,
+    whose pitch is Pillow's tap count for a crop as large as the cached image."""
+    ksize = lambda n_in, n_out: 3 if n_in <= n_out else 2 * ((n_in + n_out - 1) // n_out) + 1
+    return 3 * ((H * W + 3) // 4 * 4) + 4 * (W * ksize(SW, W) + H * ksize(SH, H) + 2 * (W + H) + 16)
+
+
+def draw_random_aug(gen, B, SH, SW, jitter=(0.8, 0.8, 0.8, 0.2), p=0.8, flip=True, scale=(0.08, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0)):
+    """The decisions of RandomResizedCrop -> RandomHorizontalFlip -> RandomApply([ColorJitter]) for B images of SH x SW, drawn from the CPU
+    generator `gen` and packed as cdf_augment_jitter_batch takes them: int32 [B, JITTER_STRIDE] =
+    top, left, h, w, flip, the four op codes in application order (0 brightness, 1 contrast, 2 saturation, 3 hue; all -1 when RandomApply
+    declined), the three factors as float32 bit patterns, the hue shift, and in word 13 (which the kernel ignores) the index of the
+    accepted crop attempt, -1 for the fallback box.
+
+    Like the rest of the device loader this reproduces torchvision's DISTRIBUTIONS, not its random stream, and all of a batch's draws are
+    vectorised (the ten crop attempts of every image at once).  torchvision is not a dependency and is not installed where this was
+    written: the rules below are restated from its documented behaviour and could not be compared against it live.
+      crop   : up to 10 attempts of area * U(scale), aspect exp(U(ln ratio)); w = round(sqrt(a r)), h = round(sqrt(a / r)); the first with
+               0 < w <= SW and 0 < h <= SH wins, top ~ randint[0, SH - h], left ~ randint[0, SW - w]; otherwise the centred box of the
+               nearest allowed aspect ratio (the whole image when its own ratio is allowed)
+      flip   : U < 0.5            apply : U <= p            order : randperm(4)
+      factors: U(max(0, 1 - x), 1 + x) as float32 for brightness, contrast, saturation; hue_factor ~ U(-hue, hue), and the shift added to
+               the 8-bit H channel is trunc(hue_factor * 255) mod 256 (the uint8 cast torchvision applies)"""
+    import math
+    f64 = torch.float64
+    area = float(SH * SW)
+    target = area * (scale[0] + (scale[1] - scale[0]) * torch.rand((B, 10), generator=gen, dtype=f64))
+    lo, hi = math.log(ratio[0]), math.log(ratio[1])
+    aspect = torch.exp(lo + (hi - lo) * torch.rand((B, 10), generator=gen, dtype=f64))
+    w = torch.round(torch.sqrt(target * aspect)).to(torch.int64)
+    h = torch.round(torch.sqrt(target / aspect)).to(torch.int64)
+    ok = (w > 0) & (w <= SW) & (h > 0) & (h <= SH)
+    any_ok = ok.any(dim=1)
+    first = torch.argmax(ok.to(torch.int8), dim=1)                          # the first accepted attempt (0 where none is: replaced below)
+    w, h = w.gather(1, first[:, None])[:, 0], h.gather(1, first[:, None])[:, 0]
+    u_top, u_left = torch.rand((B,), generator=gen, dtype=f64), torch.rand((B,), generator=gen, dtype=f64)
+    in_ratio = SW / SH
+    if in_ratio < ratio[0]:
+        fw, fh = SW, int(round(SW / ratio[0]))
+    elif in_ratio > ratio[1]:
+        fh, fw = SH, int(round(SH * ratio[1]))
+    else:
+        fw, fh = SW, SH
+    w, h = torch.where(any_ok, w, torch.tensor(fw)), torch.where(any_ok, h, torch.tensor(fh))
+    top = torch.minimum(torch.floor(u_top * (SH - h + 1)).to(torch.int64), SH - h)
+    left = torch.minimum(torch.floor(u_left * (SW - w + 1)).to(torch.int64), SW - w)
+    top, left = torch.where(any_ok, top, (SH - h) // 2), torch.where(any_ok, left, (SW - w) // 2)
+    u_flip = torch.rand((B,), generator=gen, dtype=f64)
+    u_apply = torch.rand((B,), generator=gen, dtype=f64)
+    order = torch.argsort(torch.rand((B, 4), generator=gen, dtype=f64), dim=1)
+    u_fac = torch.rand((B, 3), generator=gen, dtype=torch.float32)
+    u_hue = torch.rand((B,), generator=gen, dtype=f64)
+    out = torch.zeros((B, JITTER_STRIDE), dtype=torch.int32)
+    out[:, 0], out[:, 1], out[:, 2], out[:, 3] = top, left, h, w
+    out[:, 4] = (u_flip < 0.5) if flip else 0
+    out[:, 5:9] = -1
+    out[:, 13] = torch.where(any_ok, first, torch.tensor(-1))
+    if jitter is not None:
+        apply = u_apply <= p
+        out[:, 5:9] = torch.where(apply[:, None], order, torch.tensor(-1)).to(torch.int32)
+        # the float32 values nearest the interval's ends from INSIDE: float32(0.2) + float32(1.6) rounds to a value above 1.8
+        inf = torch.tensor(float('inf'), dtype=torch.float32)
+        f_lo = torch.tensor([max(0.0, 1.0 - x) for x in jitter[:3]], dtype=torch.float32)
+        f_hi = torch.tensor([1.0 + x for x in jitter[:3]], dtype=torch.float32)
+        f_lo = torch.where(f_lo.double() < torch.tensor([max(0.0, 1.0 - x) for x in jitter[:3]], dtype=f64), torch.nextafter(f_lo, inf), f_lo)
+        f_hi = torch.where(f_hi.double() > torch.tensor([1.0 + x for x in jitter[:3]], dtype=f64), torch.nextafter(f_hi, -inf), f_hi)
+        fac = torch.maximum(torch.minimum(f_lo + (f_hi - f_lo) * u_fac, f_hi), f_lo)
+        out[:, 9:12] = fac.contiguous().view(torch.int32)
+        hue_factor = jitter[3] * (2.0 * u_hue - 1.0)
+        out[:, 12] = (torch.trunc(hue_factor * 255.0).to(torch.int64) % 256).to(torch.int32)
+    return out
+
+
 class DeviceImageCache:
     """An image folder decoded ONCE and kept in HBM as uint8 NHWC, already past the DETERMINISTIC head of the reference's
     transform chain (`convert('RGB')`, `transforms.Resize(...)` -- done with the same PIL call on the host at cache-build time by a
@@ -646,7 +728,14 @@ class DeviceImageCache:
             except ImportError:
                 pass
         pad = recipe.pad
-        if self.SH + 2 * pad < image_size or self.SW + 2 * pad < image_size:
+        if recipe.crop == 'rrc':
+            # RandomResizedCrop scales any box to the output size (a file may be smaller than the crop); what bounds the kernel is RGB and LDS
+            if self.channels != 3:
+                raise CacheUnfit(f"{self.paths[0]}: {self.channels} channel(s); ColorJitter on the device needs an RGB folder")
+            lds = jitter_lds_bytes(self.SH, self.SW, image_size, image_size)
+            if lds > JITTER_LDS_CAP:
+                raise CacheUnfit(f"{image_size}x{image_size} crops of {self.SW}x{self.SH} images need {lds} bytes of LDS (cap {JITTER_LDS_CAP})")
+        elif self.SH + 2 * pad < image_size or self.SW + 2 * pad < image_size:
             raise CacheUnfit(f"{self.paths[0]}: {self.SW}x{self.SH} is smaller than the {image_size}x{image_size} crop")
         host = torch.empty((n, self.SH, self.SW, self.channels), dtype=torch.uint8, pin_memory=dev.type == 'cuda')
         hv = host.numpy()
@@ -684,6 +773,25 @@ class DeviceImageCache:
                                        rt.P(ox), rt.P(flip), rt.P(out), B, H, H, rt.stream(self.data))
         return out
 
+    def batch_jitter(self, idx, params_host):
+        """[B, 3, H, H] fp32 batch of the 'rrc' recipe in ONE launch: images idx (int64 [B], on the device) through crop -> Pillow's
+        bilinear resize -> mirror -> ColorJitter -> ToTensor -> t * 2 - 1 with the decisions `params_host` (CPU int32 [B, JITTER_STRIDE] as
+        `draw_random_aug` packs them).  The table travels as one pinned, non-blocking copy; the entry point checks the host copy."""
+        rt.check(self.data)
+        dev = self.data.device
+        B, H = idx.numel(), self.image_size
+        assert params_host.shape == (B, JITTER_STRIDE) and params_host.dtype == torch.int32 and params_host.device.type == 'cpu'
+        if dev.type == 'cuda':
+            pinned = torch.empty((B, JITTER_STRIDE), dtype=torch.int32, pin_memory=True)
+            pinned.copy_(params_host)
+            params_host, params_dev = pinned, pinned.to(dev, non_blocking=True)
+        else:
+            params_host = params_dev = params_host.contiguous()
+        out = torch.empty((B, 3, H, H), device=dev, dtype=torch.float32)
+        rt.lib().cdf_augment_jitter_batch(rt.P(self.data), len(self.paths), self.SH, self.SW, self.channels, rt.P(idx), rt.P(params_dev),
+                                          rt.P(params_host), rt.P(out), B, H, H, rt.stream(self.data))
+        return out
+
     def item(self, idx):
         """Image idx as the non-random chain yields it ([C, H, H]; centre crop, no mirror)."""
         dev = self.data.device
@@ -698,11 +806,20 @@ class DeviceLoader:
     short batch), batch_size images per step; with several ranks every rank takes the DistributedSampler slice perm[rank::world] of
     the SAME epoch permutation (seed + epoch on a CPU generator).  Crop and mirror follow the cache's recipe: RandomCrop offsets
     (row first, then column; none drawn when the image IS the crop size, like RandomCrop.get_params) and RandomHorizontalFlip(0.5),
-    or CenterCrop."""
+    or CenterCrop.  The 'rrc' recipe (RANDOM_AUG) draws its crop boxes, mirrors and ColorJitter decisions with `draw_random_aug` from a CPU
+    generator seeded the same way (seed + 7919 * rank), so one seed gives the same batches on the simulator and on the device;
+    `last_params` / `last_idx` hold the packed decisions and the image indices of the batch returned last, for replaying it."""
+
+    last_params = None
+    last_idx = None
 
     def __init__(self, cache, batch_size, shuffle=True, seed=123457, rank=0, world=1, drop_last=True, augment=None):
         self.cache, self.batch_size, self.shuffle, self.drop_last = cache, batch_size, shuffle, drop_last
         rec = cache.recipe
+        self.rrc = rec.crop == 'rrc'
+        if self.rrc:
+            self.aug_gen = torch.Generator()
+            self.aug_gen.manual_seed(seed + 7919 * rank)
         self.random_crop = rec.crop == 'random' if augment is None else bool(augment)
         self.flip = rec.flip if augment is None else bool(augment)
         self.seed, self.rank, self.world = seed, rank, world
@@ -712,7 +829,7 @@ class DeviceLoader:
         self.gen.manual_seed(seed + 7919 * rank)
         n = len(cache) // world if world > 1 else len(cache)
         assert n >= batch_size or not drop_last, f"{len(cache)} images over {world} ranks: fewer than one batch of {batch_size}"
-        cy, cx = cache.center()
+        cy, cx = (0, 0) if self.rrc else cache.center()
         self._cy = torch.full((batch_size,), cy, dtype=torch.int32, device=dev)
         self._cx = torch.full((batch_size,), cx, dtype=torch.int32, device=dev)
         self._noflip = torch.zeros((batch_size,), dtype=torch.int32, device=dev)
@@ -726,6 +843,7 @@ class DeviceLoader:
             perm = torch.arange(n)
         if self.world > 1:
             perm = perm[:n - n % self.world][self.rank::self.world]
+        self.order_host = perm
         self.order = perm.to(self.cache.data.device)
         self.pos = 0
         self.epoch += 1
@@ -741,6 +859,12 @@ class DeviceLoader:
             left = self.order.numel()
         B = min(B, left)                                                   # (short last batch when drop_last is off)
         idx = self.order[self.pos:self.pos + B].contiguous()
+        if self.rrc:
+            rec = self.cache.recipe
+            self.last_idx = self.order_host[self.pos:self.pos + B].clone()
+            self.last_params = draw_random_aug(self.aug_gen, B, self.cache.SH, self.cache.SW, jitter=rec.jitter, p=rec.jitter_p, flip=rec.flip)
+            self.pos += B
+            return self.cache.batch_jitter(idx, self.last_params)
         self.pos += B
         dev = self.cache.data.device
         sy, sx = self.cache.span()

@@ -28,7 +28,7 @@ extern "C" {
 /* Bumped whenever an exported signature changes incompatibly (rounds 1-3 all answered 1 while arguments were added: `tiled`,
  * `onepass`, `slots`, `tune`).  cdf_abi_version() returns the value the LIBRARY was built with; a binding compares it with the
  * header it was generated from before the first call (colddiff/_lib.py does) -- a mismatched pair would read shifted arguments. */
-#define CDF_ABI_VERSION 8
+#define CDF_ABI_VERSION 9
 
 #define CDF_E_INVALID (-1)
 #define CDF_E_UNSUPPORTED (-2)
@@ -342,6 +342,22 @@ int cdf_augment_batch(const void* cache, long long N, int S, int C, const long l
  * (Dataset_Aug2: Resize(s), RandomCrop(s, padding=4)) and defading_diffusion_gaussian.py:579-599 (DatasetCifar10). */
 int cdf_augment_batch_pad(const void* cache, long long N, int SH, int SW, int C, int pad, const long long* idx, const int* oy,
                           const int* ox, const int* flip, float* out, int B, int H, int W, void* stream);
+/* The `random_aug=True` chain of the decolorization / snowification packages (decolor_diffusion/diffusion/diffusion.py:516-526:
+ * RandomResizedCrop(size) -> RandomHorizontalFlip -> RandomApply([ColorJitter(0.8, 0.8, 0.8, 0.2)], p = 0.8) -> ToTensor -> t * 2 - 1)
+ * over the unresized RGB cache [N][SH][SW][3], ONE launch per batch, bit-equal to torchvision's PIL path: crop -> Pillow's bilinear
+ * resize to H x W (filter window clamped to the crop box) -> mirror -> the four ColorJitter ops in the row's order, each on the uint8
+ * result of the one before -> float(v) / 255 * 2 - 1.  The DECISIONS are drawn by the caller; one row of CDF_JITTER_STRIDE int32 per image:
+ *   [0] top  [1] left  [2] h  [3] w   the crop box              [4] flip (0 / 1)
+ *   [5..8]  the op list in application order: 0 brightness, 1 contrast, 2 saturation, 3 hue, -1 none (all -1: RandomApply declined)
+ *   [9..11] the brightness, contrast and saturation factors, float32 bit patterns
+ *   [12]    the hue shift added to the 8-bit H channel modulo 256 (= uint8(hue_factor * 255))          [13..15] unused
+ * `params` is what the kernel reads (device); `params_host` is the same table in host memory, which the entry point checks BEFORE the
+ * launch: a box outside the image or with h, w < 1, an op code outside -1...3, C != 3 or a geometry whose tables + working image
+ * (3 H W bytes) pass 160 KB of LDS are CDF_E_INVALID, never a launch.  idx: int64 [B] (device).  One workgroup per image; the contrast
+ * mean is an integer reduction, so results are run-to-run identical. */
+#define CDF_JITTER_STRIDE 16
+int cdf_augment_jitter_batch(const void* cache, long long N, int SH, int SW, int C, const long long* idx, const int* params,
+                             const int* params_host, float* out, int B, int H, int W, void* stream);
 
 /* The non-GEMM layers of the FID feature extractor (deblurring-diffusion-pytorch/Fid/inception.py:16-328; its BasicConv2d layers are the
  * conv GEMM entry points with act = 3 (ReLU) and BatchNorm folded into weight / bias).  Feature maps are NHWC fp32 with a pixel pitch.
