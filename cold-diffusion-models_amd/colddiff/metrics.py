@@ -1,7 +1,8 @@
 """The metric step after sampling: RMSE, SSIM and FID as the reference's evaluation code computes them
 (deblurring_diffusion_pytorch.py:1677-1702 with Fid/fid_score.py:149-343 and pytorch_msssim.ssim).
 
-* rmse / ssim run on the MI355X (cdf_loss_fwd, cdf_ssim_partial); there is no CPU fallback.
+* rmse / ssim run on the MI355X (cdf_loss_fwd, cdf_ssim_partial); there is no CPU fallback.  eval_pairs / PairStats: the same two metrics
+  of up to four candidate sets against the originals in one pass per batch (cdf_eval_pairs_partial).
 * FID = Frechet distance between the Gaussians fitted to InceptionV3 activations: the network is colddiff.inception.InceptionV3 (the
   reference's Fid/inception.py on the HIP kernels); its pretrained `pt_inception-2015-12-05` weights are a download upstream and are
   read from a local file here ($COLDDIFF_FID_WEIGHTS / torch hub cache).  Any other feature extractor
@@ -45,6 +46,62 @@ def ssim(X, Y, data_range=255, size_average=True, win_size=11, win_sigma=1.5, K=
     L.cdf_ssim_partial(P(X), P(Y), P(partial), B * C, H, W, win, C1, C2, rt.stream(X))
     per_channel = partial.sum(1).view(B, C) / float((H - win_size + 1) * (W - win_size + 1))
     return per_channel.mean() if size_average else per_channel.mean(1)
+
+
+def eval_pairs(orig, cands, shift=True, data_range=1, win_size=11, win_sigma=1.5, K=(0.01, 0.03)):
+    """The originals against 1...4 candidate batches of the same [B, C, H, W] shape in ONE launch (cdf_eval_pairs_partial): the original's
+    tile is read once, every candidate runs against it on chip.  `shift`: the batches are stored in [-1, 1] and taken as (v + 1) * 0.5.
+    -> (sse [k], ssim_sum [k]): per candidate the fp64 sums of the squared-error and of the SSIM partials (ssim_sum over every plane's valid
+    positions), as device tensors; nothing is read back."""
+    cands = list(cands)
+    assert 1 <= len(cands) <= 4, "eval_pairs takes one to four candidate batches"
+    assert orig.dim() == 4 and all(c.shape == orig.shape for c in cands), "eval_pairs takes [B, C, H, W] batches of one shape"
+    assert win_size == 11, "the HIP kernel is specialised for the 11-tap window the reference uses"
+    X = rt.check(orig).float().contiguous()
+    Ys = [c.to(X.device).float().contiguous() for c in cands]
+    B, C, H, W = X.shape
+    L = rt.lib()
+    tiles = L.cdf_ssim_tiles(H, W)
+    partial = torch.empty((2, len(Ys), B * C * tiles), device=X.device, dtype=torch.float32)
+    win = (ctypes.c_float * 11)(*_gauss_window(win_size, win_sigma).tolist())
+    C1, C2 = (K[0] * data_range) ** 2, (K[1] * data_range) ** 2
+    ptrs = [P(y) for y in Ys] + [0] * (4 - len(Ys))
+    L.cdf_eval_pairs_partial(P(X), *ptrs, len(Ys), 1 if shift else 0, P(partial[0]), P(partial[1]), B * C, H, W, win, C1, C2, rt.stream(X))
+    sums = partial.double().sum(2)
+    return sums[1], sums[0]
+
+
+class PairStats:
+    """Running RMSE / SSIM of named candidate sets against the originals over the batches of a sweep: `add(orig, cands)` per batch (one
+    launch, sums kept on the device in fp64), `result()` at the end (the one host read) ->
+    {'rmse_<name>': sqrt(SSE / count), 'ssim_<name>': S / (planes (H - 10) (W - 10))}: the whole-set `rmse` and
+    `ssim(data_range=1, size_average=True)` of the concatenated sets up to summation order."""
+
+    def __init__(self, names, shift=True):
+        self.names = tuple(names)
+        assert 1 <= len(self.names) <= 4
+        self.shift = shift
+        self.sums = None                 # [2, K] fp64 on the device: SSE, SSIM sums
+        self.count = 0                   # values per set
+        self.positions = 0               # valid SSIM positions per set
+
+    def add(self, orig, cands):
+        assert len(cands) == len(self.names)
+        sse, ss = eval_pairs(orig, cands, shift=self.shift)
+        cur = torch.stack((sse, ss))
+        self.sums = cur if self.sums is None else self.sums + cur
+        B, C, H, W = orig.shape
+        self.count += B * C * H * W
+        self.positions += B * C * (H - 10) * (W - 10)
+
+    def result(self):
+        assert self.sums is not None, "PairStats.result(): no batch was added"
+        sums = self.sums.cpu()
+        out = {}
+        for k, name in enumerate(self.names):
+            out[f'rmse_{name}'] = math.sqrt(float(sums[0, k]) / self.count)
+            out[f'ssim_{name}'] = float(sums[1, k]) / self.positions
+        return out
 
 
 # -- FID (Fid/fid_score.py) ------------------------------------------------------------------------------------------

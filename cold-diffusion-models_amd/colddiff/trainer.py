@@ -180,11 +180,15 @@ class SyntheticImages:
         return torch.randint(0, 256, self.shape, generator=self.gen, device=self.device).float() / 255 * 2 - 1
 
 
-def save_image(tensor, path, nrow=6):
-    """Minimal torchvision.utils.save_image: [B,C,H,W] in [0,1] -> PNG grid."""
-    from PIL import Image
-    t = tensor.detach().float().clamp(0, 1).cpu()
+def make_grid(tensor, nrow=8, single_as_is=True):
+    """Minimal torchvision.utils.make_grid (padding 2, pad value 0): [B,C,H,W] (or one [C,H,W] image) -> [C, rows, cols] on the host, unscaled.
+    `single_as_is`: a batch of ONE image is returned as it is, without the frame, as torchvision does."""
+    t = tensor.detach().float().cpu()
+    if t.dim() == 3:
+        t = t[None]
     B, C, H, W = t.shape
+    if B == 1 and single_as_is:
+        return t[0]
     ncol = min(nrow, B)
     nr = (B + ncol - 1) // ncol
     pad = 2
@@ -192,8 +196,20 @@ def save_image(tensor, path, nrow=6):
     for i in range(B):
         r, c = divmod(i, ncol)
         grid[:, pad + r * (H + pad): pad + r * (H + pad) + H, pad + c * (W + pad): pad + c * (W + pad) + W] = t[i]
+    return grid
+
+
+def write_grid(grid, path):
+    """[C, rows, cols] in [0,1] -> PNG (torchvision's rounding: x * 255 + 0.5, clamped, truncated)."""
+    from PIL import Image
+    C = grid.shape[0]
     arr = (grid * 255 + 0.5).clamp(0, 255).to(torch.uint8).permute(1, 2, 0).numpy()
     Image.fromarray(arr[:, :, 0] if C == 1 else arr).save(str(path))
+
+
+def save_image(tensor, path, nrow=6):
+    """Minimal torchvision.utils.save_image: [B,C,H,W] in [0,1] -> PNG grid."""
+    write_grid(make_grid(tensor.detach().float().clamp(0, 1), nrow, single_as_is=False), path)
 
 
 def _match_module_prefix(sd, target_keys):

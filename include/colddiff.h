@@ -28,7 +28,7 @@ extern "C" {
 /* Bumped whenever an exported signature changes incompatibly (rounds 1-3 all answered 1 while arguments were added: `tiled`,
  * `onepass`, `slots`, `tune`).  cdf_abi_version() returns the value the LIBRARY was built with; a binding compares it with the
  * header it was generated from before the first call (colddiff/_lib.py does) -- a mismatched pair would read shifted arguments. */
-#define CDF_ABI_VERSION 9
+#define CDF_ABI_VERSION 10
 
 #define CDF_E_INVALID (-1)
 #define CDF_E_UNSUPPORTED (-2)
@@ -378,6 +378,16 @@ int cdf_resize_bilinear_nhwc(const float* x, float* y, int ldy, int B, int C, in
 int cdf_ssim_tiles(int H, int W);
 int cdf_ssim_partial(const float* x, const float* y, float* partial, int planes, int H, int W, const float* window11, float C1,
                      float C2, void* stream);
+/* The evaluation sweep's metric step (decolor_diffusion/diffusion/diffusion.py:1121-1143): the originals x against K candidate sets
+ * c0 ... c(K-1) (1 <= K <= 4; the pointers past K are not read) of the same [planes][H][W] fp32 shape in ONE launch.  A block loads the
+ * original's tile once and runs the candidates against it one after the other: 4 (1 + K) B / pixel of HBM traffic, no temporaries.
+ * shift != 0: every value is taken as (v + 1) * 0.5 while it is loaded (the sets are stored in [-1, 1], the metrics are on [0, 1]).
+ * ssim_partial[k][plane][tile]: as cdf_ssim_partial's partial for (x, c_k), bit for bit.  sse_partial[k][plane][tile]: the sum of
+ * (x - c_k)^2 over the pixels the tile owns -- rows / columns [32 t, 32 (t + 1)), the last tile of a row / column through the image
+ * edge -- so every pixel is counted exactly once and sum(sse_partial[k]) / (planes H W) is the mean squared error. */
+int cdf_eval_pairs_partial(const float* x, const float* c0, const float* c1, const float* c2, const float* c3, int K, int shift,
+                           float* ssim_partial, float* sse_partial, int planes, int H, int W, const float* window11, float C1,
+                           float C2, void* stream);
 
 /* parameter layout <-> GEMM layout: dst[t][r][c] = src[c*s_c + r*s_r + t*s_t] (c >= C zero-filled up to ldc);
  * g[c*s_c + r*s_r + t*s_t] (+)= sum_z ws[z][t][r][c] */
