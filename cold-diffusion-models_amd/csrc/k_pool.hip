@@ -80,7 +80,7 @@ extern "C" int cdf_global_avgpool(const float* x, int ldx, float* y, int ldy, in
 }
 
 // NCHW image batch -> NHWC (pitch ldy, pad channels zeroed by the caller) bilinear resize with ATen's align_corners=False source
-// index (scale = in / out in fp32, src = scale (dst + 0.5) - 0.5 clamped at 0, neighbour clamped at in - 1), then a * v + s.
+// index (scale = in / out in fp32, src = fma(scale, dst + 0.5, -0.5) clamped at 0, neighbour clamped at in - 1), then a * v + s.
 __global__ void resize_bilinear_kernel(const float* x, float* y, int ldy, int C, int H, int W, int OH, int OW, float sh, float sw, float a, float s,
                                        long long total) {
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
@@ -89,7 +89,8 @@ __global__ void resize_bilinear_kernel(const float* x, float* y, int ldy, int C,
         const int oy = (int)(p % OH);
         p /= OH;
         const int c = (int)(p % C), b = (int)(p / C);
-        float fy = sh * ((float)oy + 0.5f) - 0.5f, fx = sw * ((float)ox + 0.5f) - 0.5f;
+        // (one rounding, as ATen's builds contract it: with two, the index is up to an ulp of 127 off -- 2.3e-6 of the neighbours' difference)
+        float fy = fmaf(sh, (float)oy + 0.5f, -0.5f), fx = fmaf(sw, (float)ox + 0.5f, -0.5f);
         fy = fy < 0.f ? 0.f : fy;
         fx = fx < 0.f ? 0.f : fx;
         const int y0 = (int)fy, x0 = (int)fx;

@@ -231,12 +231,20 @@ COVERED_AT_PRODUCTION_SHAPE = {
     # GEMM-class entry points in the plain bf16 arithmetic
     "cdf_conv_gemm_bf16": [_K + "test_conv_gemm_bf16_large"],
     "cdf_conv_wgrad_bf16": [_K + "test_conv_gemm_bf16_large"],
-    # elementwise and layout operations (no reduction, tile walk or chunk clamp that depends on the shape): the bench-shape step
+    # elementwise and layout operations: the bench-shape step.  (They have no reduction or tile walk, but they are not free of a clamp that
+    # depends on the shape: the k_misc.hip ones are grid-stride loops under a cap of 8192 blocks, and cdf_linear_small picks its 8- or
+    # 32-row form by shape -- the tests that cross those are appended below.)
     **{n: [_P2 + "test_bench_shape_fused_step_vs_oracle", _BS] for n in (
         "cdf_act_fwd", "cdf_act_bwd", "cdf_loss_fwd", "cdf_loss_bwd", "cdf_nchw_to_nhwc", "cdf_nhwc_to_nchw", "cdf_noise_qsample",
         "cdf_sinusoidal", "cdf_linear_small", "cdf_linear_small_wgrad", "cdf_pack_weight", "cdf_pack_weight_bf16")},
     "cdf_noise_step": ["test_gpu_fullsize.py::test_sampler_full_T_denoise", "test_gpu_invariance.py::test_sampler_twice_and_poisoned_bit_identical"],
 }
+# ... and past their grid caps / on the 32-row side of cdf_linear_small's threshold
+_SP = "test_small_kernels_production.py::"
+for _name, _test in (("cdf_act_fwd", "test_act_past_grid_cap"), ("cdf_act_bwd", "test_act_past_grid_cap"),
+                     ("cdf_sinusoidal", "test_sinusoidal_past_grid_cap"), ("cdf_linear_small", "test_linear_small_production"),
+                     ("cdf_linear_small_wgrad", "test_linear_small_production")):
+    COVERED_AT_PRODUCTION_SHAPE[_name].append(_SP + _test)
 # entry points with nothing shape-dependent to test at scale, with the reason
 EXEMPT = {
     "cdf_last_error": "host-side error string",
