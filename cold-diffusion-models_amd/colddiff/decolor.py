@@ -677,7 +677,9 @@ class DecolorTrainer(Trainer):
         upstream); RMSE / SSIM (/ FID when fid_func is given) of the degraded, the sampled and the directly reconstructed sets against
         the originals.  The items are the dataset's own (upstream does not pass them through `post_process_func`: with `to_lab` the
         network is fed RGB -- reproduced).  The sampler runs in its ends-only mode and the two metrics accumulate per batch
-        (`metrics.PairStats`: one launch per batch, one host read at the end); the four sets are kept, on the device, only for fid_func.
+        (`metrics.PairStats`: one launch per batch, one host read at the end); the four sets are kept, on the device, only for a plain
+        fid_func.  A fid_func with `new_stats` (`metrics.DeviceFid`) is fed per batch instead: four `FidStats`, the originals' features
+        computed once, no set kept, three `distance` calls at the end.
         -> the numbers upstream prints."""
         import numpy as np
         import torch.nn.functional as F
@@ -697,7 +699,8 @@ class DecolorTrainer(Trainer):
         all_samples = torch.stack(items)
         names = ('blur', 'deblur', 'direct_deblur')
         stats = metrics.PairStats(names)
-        kept = [[], [], [], []] if fid_func is not None else None
+        fstats = [fid_func.new_stats() for _ in range(4)] if hasattr(fid_func, 'new_stats') else None
+        kept = [[], [], [], []] if fid_func is not None and fstats is None else None
         cnt = 0
         while cnt < all_samples.shape[0]:
             og_img = all_samples[cnt: cnt + eval_batch_size].float()
@@ -711,19 +714,26 @@ class DecolorTrainer(Trainer):
             if kept is not None:
                 for dst, z in zip(kept, sets):
                     dst.append((z + 1) * 0.5)
+            if fstats is not None:
+                for st, z in zip(fstats, sets):
+                    st.add_images((z + 1) * 0.5, fid_func.model, fid_func.batch_size)
+                shape = sets[0].shape[1:]
             cnt += og_img.shape[0]
         out = stats.result()
         if kept is not None:
             orig, *cands = (torch.cat(z, dim=0) for z in kept)
             for z in [orig] + cands:
                 print(z.shape)
+        if fstats is not None:
+            for st in fstats:
+                print(torch.Size((st.n, *shape)))
         for k, (name, word) in enumerate(zip(names, ('blurry', 'deblurred', 'direct deblurred'))):
-            if kept is not None:
-                out[f'fid_{name}'] = fid_func(samples=[orig, cands[k]])
+            if fid_func is not None:
+                out[f'fid_{name}'] = fid_func.distance(fstats[0], fstats[k + 1]) if fstats is not None else fid_func(samples=[orig, cands[k]])
                 print(f"The FID of {word} images with original image is {out[f'fid_{name}']}")
             print(f"The RMSE of {word} images with original image is {out[f'rmse_{name}']}")
             print(f"The SSIM of {word} images with original image is {out[f'ssim_{name}']}")
-            if kept is not None and name != 'blur':
+            if fid_func is not None and name != 'blur':
                 print(f"Hence the improvement in FID using {'sampling' if name == 'deblur' else 'direct sampling'} is "
                       f"{out['fid_blur'] - out[f'fid_{name}']}")
         return out

@@ -156,7 +156,11 @@ class EvalMixin:
     # -- DEBLUR:1567-1702 ---------------------------------------------------------------------------------------------
     def fid_distance_decrease_from_manifold(self, fid_func=None, start=0, end=1000, batch=32):
         """Degrade -> restore every dataset image in (start, end]; RMSE / SSIM (/ FID when fid_func is given) of the degraded, the
-        sampled and the directly reconstructed images against the originals.  Returns the numbers the reference prints."""
+        sampled and the directly reconstructed images against the originals.  Returns the numbers the reference prints.
+        A fid_func with `new_stats` (`metrics.DeviceFid`) is fed batch by batch -- four `FidStats` with the originals' features computed
+        once, RMSE / SSIM through `metrics.PairStats` -- and no image set is kept; any other callable gets the concatenated sets."""
+        if hasattr(fid_func, 'new_stats'):
+            return self._fid_sweep_on_device(fid_func, start, end, batch)
         items = []
         for idx in range(len(self.ds)):
             if idx > start:
@@ -187,6 +191,38 @@ class EvalMixin:
         if fid_func is not None:
             print(f"Hence the improvement in FID using sampling is {out['fid_blur'] - out['fid_deblur']}")
             print(f"Hence the improvement in FID using direct sampling is {out['fid_blur'] - out['fid_direct_deblur']}")
+        return out
+
+    def _fid_sweep_on_device(self, fid, start, end, batch):
+        items = []
+        for idx in range(len(self.ds)):
+            if idx > start:
+                items.append(self._dataset_item(idx))
+            if end is not None and idx == end:
+                break
+        all_samples = torch.stack(items)
+        names = ('blur', 'deblur', 'direct_deblur')
+        pairs = metrics.PairStats(names)
+        fstats = [fid.new_stats() for _ in range(4)]
+        rep3 = lambda z: z.repeat(1, 3 // z.shape[1], 1, 1)
+        cnt = 0
+        while cnt < all_samples.shape[0]:
+            og_img = all_samples[cnt: cnt + batch].float()
+            X_0s, X_ts = self.ema_core.all_sample(batch_size=og_img.shape[0], img=og_img, times=None)
+            sets = [rep3(z.to(self.device)) for z in (og_img, X_ts[0], X_0s[-1], X_0s[0])]
+            pairs.add(sets[0], sets[1:])
+            for st, z in zip(fstats, sets):
+                st.add_images((z + 1) * 0.5, fid.model, fid.batch_size)
+            cnt += og_img.shape[0]
+        res, out = pairs.result(), {}
+        for k, name in enumerate(names):
+            out[f'rmse_{name}'], out[f'ssim_{name}'] = res[f'rmse_{name}'], res[f'ssim_{name}']
+            out[f'fid_{name}'] = float(fid.distance(fstats[0], fstats[k + 1]))
+            print(f"The RMSE of {name} images with original image is {out[f'rmse_{name}']}")
+            print(f"The SSIM of {name} images with original image is {out[f'ssim_{name}']}")
+            print(f"The FID of {name} images with original image is {out[f'fid_{name}']}")
+        print(f"Hence the improvement in FID using sampling is {out['fid_blur'] - out['fid_deblur']}")
+        print(f"Hence the improvement in FID using direct sampling is {out['fid_blur'] - out['fid_direct_deblur']}")
         return out
 
     # -- DEBLUR:1712-1722 ---------------------------------------------------------------------------------------------

@@ -3,6 +3,9 @@
 
 * rmse / ssim run on the MI355X (cdf_loss_fwd, cdf_ssim_partial); there is no CPU fallback.  eval_pairs / PairStats: the same two metrics
   of up to four candidate sets against the originals in one pass per batch (cdf_eval_pairs_partial).
+* FidStats / frechet_distance_device / DeviceFid: the same FID without the host -- fp64 statistics accumulated per batch on the device
+  (cdf_moments_f64) and both matrix square roots by a Newton-Schulz iteration on the fp64 matrix cores (cdf_gemm_f64).  The functions
+  of Fid/fid_score.py below them stay as they are; `calculate_frechet_distance` is the fallback when the iteration does not settle.
 * FID = Frechet distance between the Gaussians fitted to InceptionV3 activations: the network is colddiff.inception.InceptionV3 (the
   reference's Fid/inception.py on the HIP kernels); its pretrained `pt_inception-2015-12-05` weights are a download upstream and are
   read from a local file here ($COLDDIFF_FID_WEIGHTS / torch hub cache).  Any other feature extractor
@@ -147,12 +150,203 @@ def calculate_activation_statistics(samples, model, batch_size=50, dims=2048, de
     return np.mean(act, axis=0), np.cov(act, rowvar=False)
 
 
-def calculate_fid_given_samples(samples, batch_size=50, device='cuda:0', dims=2048, num_workers=1, model=None):
+def calculate_fid_given_samples(samples, batch_size=50, device='cuda:0', dims=2048, num_workers=1, model=None, on_device=False):
     """FID of two sample collections `samples = [A, B]` (Fid/fid_score.py:331-343).  `model`: a feature extractor to use instead of
-    InceptionV3([BLOCK_INDEX_BY_DIM[dims]])."""
+    InceptionV3([BLOCK_INDEX_BY_DIM[dims]]).  `on_device`: statistics and distance on the device (DeviceFid) instead of numpy / scipy."""
+    if on_device:
+        return DeviceFid(model=model, dims=dims, batch_size=batch_size, device=device)(samples=samples)
     if model is None:
         from .inception import InceptionV3
         model = InceptionV3([InceptionV3.BLOCK_INDEX_BY_DIM[dims]]).to(device)          # raises FileNotFoundError without the weight file
     m1, s1 = calculate_activation_statistics(samples[0], model, batch_size, dims, device)
     m2, s2 = calculate_activation_statistics(samples[1], model, batch_size, dims, device)
     return calculate_frechet_distance(m1, s1, m2, s2)
+
+
+# -- FID on the device ---------------------------------------------------------------------------------------------------
+def gemm_f64(a, b, out=None, alpha=1.0, diag=0.0):
+    """out[m, n] = alpha * a[m, k] @ b[k, n] + diag * I in fp64 on the matrix cores (cdf_gemm_f64); out must not alias a or b."""
+    assert a.dtype == b.dtype == torch.float64 and a.dim() == b.dim() == 2 and a.shape[1] == b.shape[0]
+    assert a.stride(1) == 1 and b.stride(1) == 1, "gemm_f64 takes row-major operands"
+    rt.check(a)
+    m, k = a.shape
+    n = b.shape[1]
+    if out is None:
+        out = torch.empty((m, n), device=a.device, dtype=torch.float64)
+    assert out.shape == (m, n) and out.dtype == torch.float64 and out.stride(1) == 1
+    rt.lib().cdf_gemm_f64(P(a), a.stride(0), P(b), b.stride(0), P(out), out.stride(0), m, n, k, float(alpha), float(diag), rt.stream(a))
+    return out
+
+
+class FidStats:
+    """Running mean / covariance of feature rows, on the device in fp64: `add(features)` per batch (one cdf_moments_f64 launch, nothing
+    read back), `mean()` / `cov()` device tensors, `result()` the one host read -> (mu, sigma) as `calculate_activation_statistics`
+    returns them.  The first batch's column mean is the pivot every row is centred on before it is squared, so the one-pass formula
+    cov = (outer - sum sum^T / n) / (n - 1) does not cancel."""
+
+    def __init__(self, dims, device):
+        self.dims = int(dims)
+        self.device = torch.device(device)
+        self.n = 0
+        self.pivot = None
+        self.sum = torch.zeros(self.dims, device=self.device, dtype=torch.float64)
+        self.outer = torch.zeros((self.dims, self.dims), device=self.device, dtype=torch.float64)     # upper block triangle (64 x 64 tiles)
+        self._mu = self._sigma = None                                                                 # set by load(): frozen
+
+    @staticmethod
+    def _rows(features):
+        if isinstance(features, (list, tuple)):
+            features = features[0]
+        rt.check(features)
+        if features.dim() == 4:                                   # not yet pooled: global spatial average, as get_activations
+            features = features.mean((2, 3))
+        return features.reshape(features.shape[0], -1).float().contiguous()
+
+    def add(self, features):
+        if self._mu is not None:
+            raise RuntimeError("FidStats.add: statistics loaded from a file are frozen")
+        f = self._rows(features)
+        assert f.shape[1] == self.dims, "FidStats(dims=%d).add: got %d features per row" % (self.dims, f.shape[1])
+        if f.shape[0] == 0:
+            return self
+        if self.pivot is None:
+            self.pivot = f.double().mean(0)
+        rt.lib().cdf_moments_f64(P(f), f.stride(0), f.shape[0], self.dims, P(self.pivot), P(self.sum), P(self.outer), self.outer.stride(0),
+                                 rt.stream(f))
+        self.n += f.shape[0]
+        return self
+
+    def add_images(self, samples, model, batch_size=50):
+        """The extractor batch by batch over `samples` [N, 3, H, W] in [0, 1] (a trailing partial batch included, as get_activations)."""
+        for s in range(0, samples.shape[0], batch_size):
+            with torch.no_grad():
+                self.add(model(samples[s:s + batch_size].to(self.device)))
+        return self
+
+    def mean(self):
+        if self._mu is not None:
+            return self._mu
+        assert self.n >= 1, "FidStats.mean(): no batch was added"
+        return self.pivot + self.sum / self.n
+
+    def cov(self):
+        if self._sigma is not None:
+            return self._sigma
+        assert self.n >= 2, "FidStats.cov(): needs at least two rows"
+        up = torch.triu(self.outer)
+        full = up + torch.triu(self.outer, 1).t()
+        return (full - torch.outer(self.sum, self.sum) / self.n) / (self.n - 1)
+
+    def result(self):
+        both = torch.cat((self.mean()[None], self.cov())).cpu().numpy()
+        return both[0], both[1:]
+
+    def save(self, path):
+        mu, sigma = self.result()
+        with open(path, "wb") as f:                               # (a file object: np.savez would append .npz to a bare name)
+            np.savez(f, mu=mu, sigma=sigma, n=np.int64(self.n))
+
+    @classmethod
+    def load(cls, path, device):
+        z = np.load(path)
+        st = cls(z["mu"].shape[0], device)
+        st._mu = torch.from_numpy(np.ascontiguousarray(z["mu"], dtype=np.float64)).to(st.device)
+        st._sigma = torch.from_numpy(np.ascontiguousarray(z["sigma"], dtype=np.float64)).to(st.device)
+        st.n = int(z["n"]) if "n" in z.files else 0
+        return st
+
+
+NS_CAP = 64            # Newton-Schulz steps per square root
+NS_FLOOR = 1e-9        # a rise of delta below this is the noise floor (see _sqrt_newton_schulz)
+
+
+def _sqrt_newton_schulz(A, max_iter=NS_CAP):
+    """sqrt of a symmetric positive semi-definite fp64 device matrix by the coupled Newton-Schulz iteration on cdf_gemm_f64:
+    c = |A|_F, Y0 = A / c, Z0 = I;  T = 1.5 I - 0.5 Z Y (one launch);  Y <- Y T, Z <- T Z;  sqrt(A) = sqrt(c) Y.
+    A rank-deficient A (every covariance of N < dims rows) makes the unbounded iteration diverge, so it stops by rule on
+    tr = Tr Y, the one scalar read per step: delta = |tr - tr_prev| / |tr|; stop with the new iterate at delta <= 1e-13, with the
+    previous one once delta_prev < NS_FLOOR = 1e-9 and delta >= delta_prev (the noise floor), fail at the cap or on a non-finite value.
+    Why 1e-9 and not 1e-6: an eigenvalue l << c enters Tr Y as ~(l / c) 1.5^k while it still grows, so delta RISES for a few steps
+    whenever a cluster of small eigenvalues is on its way up -- at d = 768, N = 64 delta went 5.93e-7, 6.70e-7, 5.44e-7, ... and the
+    iteration settled five steps later, 1.5e-6 of Tr sqrt further on.  A rise below 1e-9 at step k >= 14 can only come from eigenvalues
+    under ~1e-9 / 1.5^14 = 3e-12 of c; after convergence delta sits at 1e-13 ... 1e-11 and creeps up from there, so the first rise
+    below 1e-9 is met within a step or two of it.
+    -> (root or None, steps taken)"""
+    d = A.shape[0]
+    c = float(torch.linalg.norm(A))
+    if not math.isfinite(c):
+        return None, 0
+    if c == 0.0:
+        return torch.zeros_like(A), 0
+    Y = A / c
+    Z = torch.eye(d, device=A.device, dtype=torch.float64)
+    T, Yn, Zn = torch.empty_like(Y), torch.empty_like(Y), torch.empty_like(Y)
+    tr_prev, d_prev = float(torch.trace(Y)), math.inf
+    for it in range(1, max_iter + 1):
+        gemm_f64(Z, Y, out=T, alpha=-0.5, diag=1.5)
+        gemm_f64(Y, T, out=Yn)
+        gemm_f64(T, Z, out=Zn)
+        tr = float(torch.trace(Yn))
+        if not math.isfinite(tr) or tr == 0.0:
+            return None, it
+        delta = abs(tr - tr_prev) / abs(tr)
+        if delta <= 1e-13:
+            return Yn * math.sqrt(c), it
+        if d_prev < NS_FLOOR and delta >= d_prev:
+            return Y * math.sqrt(c), it
+        Y, Yn = Yn, Y
+        Z, Zn = Zn, Z
+        tr_prev, d_prev = tr, delta
+    return None, max_iter
+
+
+def frechet_distance_device(s1, s2, eps=1e-6, _max_iter=NS_CAP, _info=None):
+    """d^2 = |mu1 - mu2|^2 + Tr C1 + Tr C2 - 2 Tr sqrt(C1 C2) of two FidStats, on the device: Tr sqrt(C1 C2) = Tr sqrt(S1 C2 S1) with
+    S1 = sqrt(C1), both roots by `_sqrt_newton_schulz`, M = S1 C2 S1 symmetrised in between.  If a root does not settle (cap, non-finite
+    value) one line says so and the host `calculate_frechet_distance(..., eps)` of the same statistics is returned.
+    `_info` (a dict) receives the step counts and Tr sqrt(C1 C2)."""
+    mu1, mu2, C1, C2 = s1.mean(), s2.mean(), s1.cov(), s2.cov()
+    assert mu1.shape == mu2.shape, 'Training and test mean vectors have different lengths'
+    assert C1.shape == C2.shape, 'Training and test covariances have different dimensions'
+    info = {} if _info is None else _info
+    info.update(iters=(0, 0), tr_sqrt=None, fallback=False)
+    S1, it1 = _sqrt_newton_schulz(C1, _max_iter)
+    it2, tr_sqrt = 0, None
+    if S1 is not None:
+        M = gemm_f64(S1, gemm_f64(C2, S1))
+        M = (M + M.t()) * 0.5
+        S2, it2 = _sqrt_newton_schulz(M, _max_iter)
+        if S2 is not None:
+            tr_sqrt = float(torch.trace(S2))
+    info["iters"] = (it1, it2)
+    diff = mu1 - mu2
+    if tr_sqrt is None or not math.isfinite(tr_sqrt):
+        print('fid on the device: the square-root iteration did not settle within %d steps; using the host calculate_frechet_distance'
+              % _max_iter)
+        info["fallback"] = True
+        return float(calculate_frechet_distance(mu1.cpu().numpy(), C1.cpu().numpy(), mu2.cpu().numpy(), C2.cpu().numpy(), eps))
+    info["tr_sqrt"] = tr_sqrt
+    return float(diff.dot(diff) + torch.trace(C1) + torch.trace(C2)) - 2.0 * tr_sqrt
+
+
+class DeviceFid:
+    """FID with the statistics and the distance on the device: a drop-in `fid_func` (`__call__(samples=[A, B]) -> float`) for the
+    Trainers' evaluation methods, which feed its `new_stats()` per batch instead of keeping the image sets."""
+
+    def __init__(self, model=None, dims=2048, batch_size=50, device='cuda:0'):
+        if model is None:
+            from .inception import InceptionV3
+            model = InceptionV3([InceptionV3.BLOCK_INDEX_BY_DIM[dims]]).to(device)      # raises FileNotFoundError without the weight file
+        self.model, self.dims, self.batch_size, self.device = model, dims, batch_size, torch.device(device)
+
+    def new_stats(self):
+        return FidStats(self.dims, self.device)
+
+    def stats(self, samples):
+        return self.new_stats().add_images(samples, self.model, self.batch_size)
+
+    def distance(self, s1, s2):
+        return frechet_distance_device(s1, s2)
+
+    def __call__(self, samples):
+        return self.distance(self.stats(samples[0]), self.stats(samples[1]))

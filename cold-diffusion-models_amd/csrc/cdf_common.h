@@ -67,6 +67,32 @@ static inline void cdf_raise_lds_limit() {
 #define CDF_WAVE_SYNC() __builtin_amdgcn_wave_barrier()
 #endif
 
+// ---- 16 x 16 x 4 fp64 MFMA (v_mfma_f64_16x16x4_f64) ----------------------------------------------------------
+// One double per lane for A and for B: lane l holds A[row l & 15][k = l >> 4] and B[k = l >> 4][col l & 15].  C/D: 4 doubles per lane,
+// register r of lane l is row (l >> 4) + 4 r, column l & 15 -- NOT the fp32 forms' row (l >> 4) * 4 + r.
+// The simulator has no fp64 MFMA: the instruction is restated here on its wave exchange (products summed in k order, fused).
+typedef double f64x4_t __attribute__((ext_vector_type(4)));
+#ifdef CDF_EMU
+static inline f64x4_t cdf_mfma_f64_16x16x4(double a, double b, f64x4_t c) {
+    const int w = hipemu::wave_id(), l = hipemu::lane_id();
+    double av[4][4], bv[4];
+    memcpy(&hipemu::g.wave_u[w][l], &a, 8);
+    hipemu::wave_barrier();
+    for (int r = 0; r < 4; ++r)
+        for (int k = 0; k < 4; ++k) memcpy(&av[r][k], &hipemu::g.wave_u[w][k * 16 + (l >> 4) + 4 * r], 8);
+    hipemu::wave_barrier();
+    memcpy(&hipemu::g.wave_u[w][l], &b, 8);
+    hipemu::wave_barrier();
+    for (int k = 0; k < 4; ++k) memcpy(&bv[k], &hipemu::g.wave_u[w][k * 16 + (l & 15)], 8);
+    hipemu::wave_barrier();
+    for (int r = 0; r < 4; ++r)
+        for (int k = 0; k < 4; ++k) c[r] = fma(av[r][k], bv[k], c[r]);
+    return c;
+}
+#else
+#define cdf_mfma_f64_16x16x4(a, b, c) __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0)
+#endif
+
 // ---- 32 x 32 MFMA accumulators (f32x16_t) ----------------------------------------------------------------
 // Lane l holds column l & 31 of the block; its register r is row cdf_acc_row(r, l >> 5).
 constexpr int cdf_acc_row(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }

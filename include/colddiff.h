@@ -28,7 +28,7 @@ extern "C" {
 /* Bumped whenever an exported signature changes incompatibly (rounds 1-3 all answered 1 while arguments were added: `tiled`,
  * `onepass`, `slots`, `tune`).  cdf_abi_version() returns the value the LIBRARY was built with; a binding compares it with the
  * header it was generated from before the first call (colddiff/_lib.py does) -- a mismatched pair would read shifted arguments. */
-#define CDF_ABI_VERSION 10
+#define CDF_ABI_VERSION 11
 
 #define CDF_E_INVALID (-1)
 #define CDF_E_UNSUPPORTED (-2)
@@ -388,6 +388,19 @@ int cdf_ssim_partial(const float* x, const float* y, float* partial, int planes,
 int cdf_eval_pairs_partial(const float* x, const float* c0, const float* c1, const float* c2, const float* c3, int K, int shift,
                            float* ssim_partial, float* sse_partial, int planes, int H, int W, const float* window11, float C1,
                            float C2, void* stream);
+
+/* FID on the device (Fid/fid_score.py:149-283): fp64 statistics of feature batches and the fp64 GEMM of the Frechet distance's matrix
+ * square roots, both on the f64 matrix-core instruction (v_mfma_f64_16x16x4_f64).
+ * cdf_moments_f64: x [n][d] fp32 (row pitch ldx); every value is widened to fp64 and the pivot (d doubles) subtracted in fp64:
+ *   sum[j] += sum_i (x_ij - pivot_j);   outer[j][k] += sum_i (x_ij - pivot_j)(x_ik - pivot_k)   (outer: [d][d] fp64, row pitch ldo)
+ * for the 64 x 64 tiles of the UPPER block triangle only (tile row <= tile column; a diagonal tile is written whole): the tiles below
+ * it and everything outside [d][d] are neither read nor written.  Every tile belongs to one workgroup, which adds to what it read: no
+ * atomics, successive launches on one stream accumulate deterministically.  n >= 1, d >= 1, ldx >= d, ldo >= d.
+ * cdf_gemm_f64: c[m][n] = alpha * a[m][k] b[k][n] + diag * I, row-major fp64 with row pitches lda / ldb / ldc; any m, n, k >= 1;
+ * c must not overlap a or b. */
+int cdf_moments_f64(const float* x, int ldx, int n, int d, const double* pivot, double* sum, double* outer, int ldo, void* stream);
+int cdf_gemm_f64(const double* a, int lda, const double* b, int ldb, double* c, int ldc, int m, int n, int k, double alpha, double diag,
+                 void* stream);
 
 /* parameter layout <-> GEMM layout: dst[t][r][c] = src[c*s_c + r*s_r + t*s_t] (c >= C zero-filled up to ldc);
  * g[c*s_c + r*s_r + t*s_t] (+)= sum_z ws[z][t][r][c] */
