@@ -672,7 +672,7 @@ class DecolorTrainer(Trainer):
                 Image.fromarray(np.concatenate(framed, axis=1)).save(str(self.results_folder / f'all_{cnt}.png'))
                 cnt += 1
 
-    def fid_distance_decrease_from_manifold(self, fid_func, start=0, end=1000, eval_batch_size=16):
+    def fid_distance_decrease_from_manifold(self, fid_func, start=0, end=1000, eval_batch_size=16, shard=False):
         """Degrade -> restore the dataset items idx with start < idx <= end of a `np.random.permutation` walk (numpy's global stream, as
         upstream); RMSE / SSIM (/ FID when fid_func is given) of the degraded, the sampled and the directly reconstructed sets against
         the originals.  The items are the dataset's own (upstream does not pass them through `post_process_func`: with `to_lab` the
@@ -680,31 +680,45 @@ class DecolorTrainer(Trainer):
         (`metrics.PairStats`: one launch per batch, one host read at the end); the four sets are kept, on the device, only for a plain
         fid_func.  A fid_func with `new_stats` (`metrics.DeviceFid`) is fed per batch instead: four `FidStats`, the originals' features
         computed once, no set kept, three `distance` calls at the end.
+        `shard`: under `torch.distributed.run` with W > 1 ranks, rank r runs the batches k with k % W == r of rank 0's permutation (every
+        rank still draws its own, so its numpy stream advances as without the keyword), the accumulators are all-reduced at the end, every
+        rank returns the same dict and rank 0 prints (fid_func: None or one with `new_stats`).
         -> the numbers upstream prints."""
         import numpy as np
         import torch.nn.functional as F
         from . import metrics
-        print(len(self.ds))
+        from .evaluate import shard_ranks
+        rank, world = shard_ranks(shard, fid_func)
+        say = print if rank == 0 else (lambda *a, **kw: None)
+        say(len(self.ds))
         perp = np.random.permutation(len(self.ds))
+        if world > 1:
+            walk = torch.from_numpy(perp).to(self.device)
+            torch.distributed.broadcast(walk, src=0)
+            perp = walk.cpu().numpy()
         items = []
         for idx in range(len(self.ds)):
             img = self._dataset_item(int(perp[idx]))
             if idx > start:
                 items.append(img)
             if idx % 1000 == 0:
-                print(idx)
+                say(idx)
             if end != None and idx == end:                     # noqa: E711
-                print(idx)
+                say(idx)
                 break
         all_samples = torch.stack(items)
         names = ('blur', 'deblur', 'direct_deblur')
         stats = metrics.PairStats(names)
         fstats = [fid_func.new_stats() for _ in range(4)] if hasattr(fid_func, 'new_stats') else None
         kept = [[], [], [], []] if fid_func is not None and fstats is None else None
-        cnt = 0
+        cnt = nbatch = 0
+        shape = None                                           # (a rank whose share is empty never sees one; rank 0, which prints, has batch 0)
         while cnt < all_samples.shape[0]:
             og_img = all_samples[cnt: cnt + eval_batch_size].float()
-            print(og_img.shape)
+            cnt, nbatch = cnt + og_img.shape[0], nbatch + 1
+            if (nbatch - 1) % world != rank:
+                continue
+            say(og_img.shape)
             xt, direct, final = self.ema_core.all_sample(batch_size=og_img.shape[0], img=og_img, times=None, ends_only=True)
             sets = [og_img, xt, final, direct]
             if og_img.shape[2] > 256:
@@ -718,24 +732,27 @@ class DecolorTrainer(Trainer):
                 for st, z in zip(fstats, sets):
                     st.add_images((z + 1) * 0.5, fid_func.model, fid_func.batch_size)
                 shape = sets[0].shape[1:]
-            cnt += og_img.shape[0]
+        if world > 1:
+            stats.all_reduce(device=self.device)
+            for st in fstats or ():
+                st.all_reduce()
         out = stats.result()
         if kept is not None:
             orig, *cands = (torch.cat(z, dim=0) for z in kept)
             for z in [orig] + cands:
                 print(z.shape)
-        if fstats is not None:
+        if fstats is not None and rank == 0:
             for st in fstats:
                 print(torch.Size((st.n, *shape)))
         for k, (name, word) in enumerate(zip(names, ('blurry', 'deblurred', 'direct deblurred'))):
             if fid_func is not None:
                 out[f'fid_{name}'] = fid_func.distance(fstats[0], fstats[k + 1]) if fstats is not None else fid_func(samples=[orig, cands[k]])
-                print(f"The FID of {word} images with original image is {out[f'fid_{name}']}")
-            print(f"The RMSE of {word} images with original image is {out[f'rmse_{name}']}")
-            print(f"The SSIM of {word} images with original image is {out[f'ssim_{name}']}")
+                say(f"The FID of {word} images with original image is {out[f'fid_{name}']}")
+            say(f"The RMSE of {word} images with original image is {out[f'rmse_{name}']}")
+            say(f"The SSIM of {word} images with original image is {out[f'ssim_{name}']}")
             if fid_func is not None and name != 'blur':
-                print(f"Hence the improvement in FID using {'sampling' if name == 'deblur' else 'direct sampling'} is "
-                      f"{out['fid_blur'] - out[f'fid_{name}']}")
+                say(f"Hence the improvement in FID using {'sampling' if name == 'deblur' else 'direct sampling'} is "
+                    f"{out['fid_blur'] - out[f'fid_{name}']}")
         return out
 
     # figure code (cv2 text, matplotlib) and the two methods that are dead upstream (`metrics` is never imported there): closed, with the

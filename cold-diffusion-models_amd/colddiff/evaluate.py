@@ -42,6 +42,19 @@ def _create_folder(path):
     os.makedirs(path, exist_ok=True)
 
 
+def shard_ranks(shard, fid_func=None):
+    """(rank, world) an evaluation sweep splits its batches over: (0, 1) unless `shard` is set AND the process is one of several of an
+    initialised process group (`python -m torch.distributed.run`).  A sharded sweep merges per-rank accumulators, so its fid_func must be
+    None or feed `FidStats` (`new_stats`): a plain callable wants the whole image sets, which no rank holds."""
+    import torch.distributed as dist
+    if not shard or not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() == 1:
+        return 0, 1
+    if fid_func is not None and not hasattr(fid_func, 'new_stats'):
+        raise ValueError("shard=True takes fid_func=None or a fid_func with new_stats (metrics.DeviceFid): a plain callable needs the "
+                         "whole image sets, and every rank holds only its own batches")
+    return dist.get_rank(), dist.get_world_size()
+
+
 class EvalMixin:
     """Evaluation methods of the reference Trainer; mixed into colddiff.trainer.Trainer."""
 
@@ -154,13 +167,16 @@ class EvalMixin:
         return xt, direct_recons, all_images
 
     # -- DEBLUR:1567-1702 ---------------------------------------------------------------------------------------------
-    def fid_distance_decrease_from_manifold(self, fid_func=None, start=0, end=1000, batch=32):
+    def fid_distance_decrease_from_manifold(self, fid_func=None, start=0, end=1000, batch=32, shard=False):
         """Degrade -> restore every dataset image in (start, end]; RMSE / SSIM (/ FID when fid_func is given) of the degraded, the
         sampled and the directly reconstructed images against the originals.  Returns the numbers the reference prints.
         A fid_func with `new_stats` (`metrics.DeviceFid`) is fed batch by batch -- four `FidStats` with the originals' features computed
-        once, RMSE / SSIM through `metrics.PairStats` -- and no image set is kept; any other callable gets the concatenated sets."""
-        if hasattr(fid_func, 'new_stats'):
-            return self._fid_sweep_on_device(fid_func, start, end, batch)
+        once, RMSE / SSIM through `metrics.PairStats` -- and no image set is kept; any other callable gets the concatenated sets.
+        `shard`: under `torch.distributed.run` with W > 1 ranks, rank r runs the batches k with k % W == r, the accumulators are
+        all-reduced at the end, every rank returns the same dict and rank 0 prints (fid_func: None or one with `new_stats`)."""
+        rank, world = shard_ranks(shard, fid_func)
+        if hasattr(fid_func, 'new_stats') or world > 1:
+            return self._fid_sweep_on_device(fid_func, start, end, batch, rank, world)
         items = []
         for idx in range(len(self.ds)):
             if idx > start:
@@ -193,7 +209,9 @@ class EvalMixin:
             print(f"Hence the improvement in FID using direct sampling is {out['fid_blur'] - out['fid_direct_deblur']}")
         return out
 
-    def _fid_sweep_on_device(self, fid, start, end, batch):
+    def _fid_sweep_on_device(self, fid, start, end, batch, rank=0, world=1):
+        """The sweep on per-batch accumulators.  world > 1: this rank's share of the batches (every `world`-th, from `rank`; possibly
+        none), then one all-reduce of the accumulators; `fid` may be None then (RMSE / SSIM only)."""
         items = []
         for idx in range(len(self.ds)):
             if idx > start:
@@ -203,26 +221,36 @@ class EvalMixin:
         all_samples = torch.stack(items)
         names = ('blur', 'deblur', 'direct_deblur')
         pairs = metrics.PairStats(names)
-        fstats = [fid.new_stats() for _ in range(4)]
+        fstats = [fid.new_stats() for _ in range(4)] if fid is not None else []
         rep3 = lambda z: z.repeat(1, 3 // z.shape[1], 1, 1)
-        cnt = 0
+        cnt = nbatch = 0
         while cnt < all_samples.shape[0]:
             og_img = all_samples[cnt: cnt + batch].float()
+            cnt, nbatch = cnt + og_img.shape[0], nbatch + 1
+            if (nbatch - 1) % world != rank:
+                continue
             X_0s, X_ts = self.ema_core.all_sample(batch_size=og_img.shape[0], img=og_img, times=None)
             sets = [rep3(z.to(self.device)) for z in (og_img, X_ts[0], X_0s[-1], X_0s[0])]
             pairs.add(sets[0], sets[1:])
             for st, z in zip(fstats, sets):
                 st.add_images((z + 1) * 0.5, fid.model, fid.batch_size)
-            cnt += og_img.shape[0]
+        if world > 1:
+            pairs.all_reduce(device=self.device)
+            for st in fstats:
+                st.all_reduce()
+        say = print if rank == 0 else (lambda *a, **kw: None)
         res, out = pairs.result(), {}
         for k, name in enumerate(names):
             out[f'rmse_{name}'], out[f'ssim_{name}'] = res[f'rmse_{name}'], res[f'ssim_{name}']
-            out[f'fid_{name}'] = float(fid.distance(fstats[0], fstats[k + 1]))
-            print(f"The RMSE of {name} images with original image is {out[f'rmse_{name}']}")
-            print(f"The SSIM of {name} images with original image is {out[f'ssim_{name}']}")
-            print(f"The FID of {name} images with original image is {out[f'fid_{name}']}")
-        print(f"Hence the improvement in FID using sampling is {out['fid_blur'] - out['fid_deblur']}")
-        print(f"Hence the improvement in FID using direct sampling is {out['fid_blur'] - out['fid_direct_deblur']}")
+            if fid is not None:
+                out[f'fid_{name}'] = float(fid.distance(fstats[0], fstats[k + 1]))
+            say(f"The RMSE of {name} images with original image is {out[f'rmse_{name}']}")
+            say(f"The SSIM of {name} images with original image is {out[f'ssim_{name}']}")
+            if fid is not None:
+                say(f"The FID of {name} images with original image is {out[f'fid_{name}']}")
+        if fid is not None:
+            say(f"Hence the improvement in FID using sampling is {out['fid_blur'] - out['fid_deblur']}")
+            say(f"Hence the improvement in FID using direct sampling is {out['fid_blur'] - out['fid_direct_deblur']}")
         return out
 
     # -- DEBLUR:1712-1722 ---------------------------------------------------------------------------------------------
@@ -245,17 +273,24 @@ class GenEvalMixin:
         """The starting images `sample_and_save_for_fid` samples from, one batch (per package)."""
         raise NotImplementedError
 
-    def sample_and_save_for_fid(self, noise=0, num_samples=6400, bs=None):
+    def sample_and_save_for_fid(self, noise=0, num_samples=6400, bs=None, shard=False):
+        """`shard`: under `torch.distributed.run` with W > 1 ranks, round k is rank k % W's and writes the files k bs ... k bs + bs - 1, so
+        the folder ends up with the names one process writes; every rank waits for the others and returns the total count."""
         bs = self._fid_batch if bs is None else bs
+        rank, world = shard_ranks(shard)
         out_folder = f'{self.results_folder}_out'
         _create_folder(out_folder)
         cnt = 0
-        for _ in range(int(num_samples / bs)):
-            og_img = self._seed_images(bs)
-            xt, direct_recons, all_images = self._gen(bs, og_img, noise)
-            for i in range(all_images.shape[0]):
-                self._save(all_images[i:i + 1], f'{out_folder}/sample-x0-{cnt}.png', nrow=1)
-                cnt += 1
+        for k in range(int(num_samples / bs)):
+            if k % world == rank:
+                og_img = self._seed_images(bs)
+                xt, direct_recons, all_images = self._gen(bs, og_img, noise)
+                for i in range(all_images.shape[0]):
+                    self._save(all_images[i:i + 1], f'{out_folder}/sample-x0-{cnt + i}.png', nrow=1)
+            cnt += all_images.shape[0] if world == 1 else bs          # (sharded: the count cannot depend on a round another rank ran)
+        if world > 1:
+            from . import parallel
+            parallel.milestone_barrier()
         return cnt
 
     def _gen(self, bs, og_img, noise):

@@ -4,7 +4,8 @@
 * rmse / ssim run on the MI355X (cdf_loss_fwd, cdf_ssim_partial); there is no CPU fallback.  eval_pairs / PairStats: the same two metrics
   of up to four candidate sets against the originals in one pass per batch (cdf_eval_pairs_partial).
 * FidStats / frechet_distance_device / DeviceFid: the same FID without the host -- fp64 statistics accumulated per batch on the device
-  (cdf_moments_f64) and both matrix square roots by a Newton-Schulz iteration on the fp64 matrix cores (cdf_gemm_f64).  The functions
+  (cdf_moments_f64; `merge` / `all_reduce` join the accumulators of several ranks, cdf_moments_merge_f64) and both matrix square
+  roots by a Newton-Schulz iteration on the fp64 matrix cores (cdf_gemm_f64).  The functions
   of Fid/fid_score.py below them stay as they are; `calculate_frechet_distance` is the fallback when the iteration does not settle.
 * FID = Frechet distance between the Gaussians fitted to InceptionV3 activations: the network is colddiff.inception.InceptionV3 (the
   reference's Fid/inception.py on the HIP kernels); its pretrained `pt_inception-2015-12-05` weights are a download upstream and are
@@ -74,6 +75,32 @@ def eval_pairs(orig, cands, shift=True, data_range=1, win_size=11, win_sigma=1.5
     return sums[1], sums[0]
 
 
+def _group_size(group=None):
+    """Ranks of `group` (the default group for None); 1 without an initialised process group."""
+    import torch.distributed as dist
+    if not (dist.is_available() and dist.is_initialized()):
+        return 1
+    return dist.get_world_size(group)
+
+
+def _exchange_device():
+    """Where a rank that holds no tensor of its own puts its part of an exchange: the GPU when there is one (RCCL carries nothing else)."""
+    return torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
+
+
+def _gather_rows(mine, group=None):
+    """`mine` (one flat tensor of the same length on every rank) of every rank of `group` -> [world, len], rows in rank order.  The
+    tensors travel as they are -- device tensors through RCCL, or through gloo (which stages them on the host itself), as
+    `parallel.GradSync` hands its buckets to the backend in use: one broadcast per rank into that rank's row."""
+    import torch.distributed as dist
+    world, me = dist.get_world_size(group), dist.get_rank(group)
+    rows = torch.empty((world, mine.numel()), device=mine.device, dtype=mine.dtype)
+    rows[me].copy_(mine)
+    for r in range(world):
+        dist.broadcast(rows[r], src=dist.get_global_rank(group, r) if group is not None else r, group=group)
+    return rows
+
+
 class PairStats:
     """Running RMSE / SSIM of named candidate sets against the originals over the batches of a sweep: `add(orig, cands)` per batch (one
     launch, sums kept on the device in fp64), `result()` at the end (the one host read) ->
@@ -96,6 +123,36 @@ class PairStats:
         B, C, H, W = orig.shape
         self.count += B * C * H * W
         self.positions += B * C * (H - 10) * (W - 10)
+
+    def merge(self, other):
+        """Adds the sums and counts of `other` (the same names; an instance without a batch adds nothing) -> self."""
+        assert other.names == self.names, "PairStats.merge: the candidate sets differ"
+        if other.sums is not None:
+            cur = other.sums.to(self.sums.device) if self.sums is not None else other.sums.clone()
+            self.sums = cur if self.sums is None else self.sums + cur
+        self.count += other.count
+        self.positions += other.positions
+        return self
+
+    def all_reduce(self, group=None, device=None):
+        """The sums of every rank of `group`, added in rank order in fp64 on every rank (bit-identical everywhere); a rank without a batch
+        contributes zeros (on `device`: where the other ranks keep their sums).  One small exchange per sweep; without a process group,
+        or alone in it, nothing happens.  -> self"""
+        world = _group_size(group)
+        if world == 1:
+            return self
+        dev = self.sums.device if self.sums is not None else torch.device(device) if device is not None else _exchange_device()
+        mine = torch.zeros(2 * len(self.names) + 2, device=dev, dtype=torch.float64)
+        if self.sums is not None:
+            mine[:-2] = self.sums.reshape(-1)
+        mine[-2], mine[-1] = self.count, self.positions              # (integers far below 2^53)
+        parts = _gather_rows(mine, group)
+        total = parts[0].clone()
+        for r in range(1, world):
+            total = total + parts[r]
+        tail = total[-2:].cpu()
+        self.sums, self.count, self.positions = total[:-2].reshape(2, len(self.names)).clone(), int(tail[0]), int(tail[1])
+        return self
 
     def result(self):
         assert self.sums is not None, "PairStats.result(): no batch was added"
@@ -192,6 +249,7 @@ class FidStats:
         self.sum = torch.zeros(self.dims, device=self.device, dtype=torch.float64)
         self.outer = torch.zeros((self.dims, self.dims), device=self.device, dtype=torch.float64)     # upper block triangle (64 x 64 tiles)
         self._mu = self._sigma = None                                                                 # set by load(): frozen
+        self._n_known = True                                                                          # False: loaded from a file without n
 
     @staticmethod
     def _rows(features):
@@ -214,6 +272,63 @@ class FidStats:
         rt.lib().cdf_moments_f64(P(f), f.stride(0), f.shape[0], self.dims, P(self.pivot), P(self.sum), P(self.outer), self.outer.stride(0),
                                  rt.stream(f))
         self.n += f.shape[0]
+        return self
+
+    def _parts(self):
+        """(n, pivot, sum, outer) as `merge` reads them; loaded statistics enter as pivot = mu, sum = 0, outer = (n - 1) sigma."""
+        if self._mu is None:
+            return self.n, self.pivot, self.sum, self.outer
+        if not self._n_known:
+            raise ValueError("FidStats.merge: the statistics were loaded from a file saved without n (the row count weighs them)")
+        return self.n, self._mu, torch.zeros_like(self._mu), self._sigma * float(self.n - 1)
+
+    def merge(self, other):
+        """Adds the rows `other` has seen: one cdf_moments_merge_f64 launch, nothing read back; `self` then holds the statistics of the
+        union of rows, on its own pivot.  `other` is left as it is.  An empty `other` is a no-op; an empty `self` adopts a copy.  -> self"""
+        if self._mu is not None:
+            raise RuntimeError("FidStats.merge: statistics loaded from a file are frozen")
+        if other.dims != self.dims:
+            raise ValueError("FidStats(dims=%d).merge: the other statistics have dims=%d" % (self.dims, other.dims))
+        n, pivot, s, outer = other._parts()
+        if n == 0:
+            return self
+        pivot, s, outer = (z.to(self.device) for z in (pivot, s, outer))
+        if self.n == 0:
+            self.pivot = pivot.clone()
+            self.sum.copy_(s)
+            self.outer.copy_(outer)
+        else:
+            assert outer.stride(1) == 1 and s.is_contiguous() and pivot.is_contiguous()
+            rt.check(outer)
+            rt.lib().cdf_moments_merge_f64(float(n), P(pivot), P(s), P(outer), outer.stride(0), P(self.pivot), P(self.sum), P(self.outer),
+                                           self.outer.stride(0), self.dims, rt.stream(outer))
+        self.n += n
+        return self
+
+    def all_reduce(self, group=None):
+        """The statistics of the rows of EVERY rank of `group`, on every rank: each rank's (n, pivot, sum, outer) is gathered (one
+        exchange per sweep) and the parts are merged in rank order, starting from the first rank that saw a row -- so every rank ends
+        with bit-identical statistics whatever order the parts arrived in.  Ranks that added nothing take part.  Without a process group,
+        or alone in it, `self` is returned untouched."""
+        world = _group_size(group)
+        if world == 1:
+            return self
+        if self._mu is not None:
+            raise RuntimeError("FidStats.all_reduce: statistics loaded from a file are frozen")
+        d = self.dims
+        mine = torch.zeros(1 + 2 * d + d * d, device=self.device, dtype=torch.float64)
+        mine[0] = self.n
+        if self.n:
+            mine[1:1 + d], mine[1 + d:1 + 2 * d] = self.pivot, self.sum
+            mine[1 + 2 * d:] = self.outer.reshape(-1)
+        rows = _gather_rows(mine, group)
+        counts = [int(v) for v in rows[:, 0].cpu()]
+        total, part = FidStats(d, self.device), FidStats(d, self.device)
+        for r in range(world):
+            if counts[r]:                                             # (`part`: views of row r; merge copies what it adopts)
+                part.n, part.pivot, part.sum, part.outer = counts[r], rows[r, 1:1 + d], rows[r, 1 + d:1 + 2 * d], rows[r, 1 + 2 * d:].view(d, d)
+                total.merge(part)
+        self.n, self.pivot, self.sum, self.outer = total.n, total.pivot, total.sum, total.outer
         return self
 
     def add_images(self, samples, model, batch_size=50):
@@ -253,6 +368,7 @@ class FidStats:
         st._mu = torch.from_numpy(np.ascontiguousarray(z["mu"], dtype=np.float64)).to(st.device)
         st._sigma = torch.from_numpy(np.ascontiguousarray(z["sigma"], dtype=np.float64)).to(st.device)
         st.n = int(z["n"]) if "n" in z.files else 0
+        st._n_known = "n" in z.files
         return st
 
 

@@ -28,7 +28,7 @@ extern "C" {
 /* Bumped whenever an exported signature changes incompatibly (rounds 1-3 all answered 1 while arguments were added: `tiled`,
  * `onepass`, `slots`, `tune`).  cdf_abi_version() returns the value the LIBRARY was built with; a binding compares it with the
  * header it was generated from before the first call (colddiff/_lib.py does) -- a mismatched pair would read shifted arguments. */
-#define CDF_ABI_VERSION 11
+#define CDF_ABI_VERSION 12
 
 #define CDF_E_INVALID (-1)
 #define CDF_E_UNSUPPORTED (-2)
@@ -397,8 +397,17 @@ int cdf_eval_pairs_partial(const float* x, const float* c0, const float* c1, con
  * it and everything outside [d][d] are neither read nor written.  Every tile belongs to one workgroup, which adds to what it read: no
  * atomics, successive launches on one stream accumulate deterministically.  n >= 1, d >= 1, ldx >= d, ldo >= d.
  * cdf_gemm_f64: c[m][n] = alpha * a[m][k] b[k][n] + diag * I, row-major fp64 with row pitches lda / ldb / ldc; any m, n, k >= 1;
- * c must not overlap a or b. */
+ * c must not overlap a or b.
+ * cdf_moments_merge_f64: accumulator b (n_b rows centred on pivot_b: sum_b, outer_b) added to accumulator a, re-centred on a's pivot.
+ *   delta = pivot_b - pivot_a;   sum_a[i] += sum_b[i] + n_b delta_i;
+ *   outer_a[i][j] += outer_b[i][j] + delta_i sum_b[j] + sum_b[i] delta_j + n_b delta_i delta_j
+ * in plain fp64, one thread per element, for the same tiles as cdf_moments_f64 (a diagonal tile whole; nothing else is read or
+ * written); a then holds the moments of the union of rows on pivot_a.  b and both pivots are read-only.  d >= 1, ldo_a >= d,
+ * ldo_b >= d, n_b >= 1, outer_a != outer_b, sum_a != sum_b.  An evaluation-time call (once per rank and sweep), never a training or
+ * sampler step's. */
 int cdf_moments_f64(const float* x, int ldx, int n, int d, const double* pivot, double* sum, double* outer, int ldo, void* stream);
+int cdf_moments_merge_f64(double n_b, const double* pivot_b, const double* sum_b, const double* outer_b, int ldo_b,
+                          const double* pivot_a, double* sum_a, double* outer_a, int ldo_a, int d, void* stream);
 int cdf_gemm_f64(const double* a, int lda, const double* b, int ldb, double* c, int ldc, int m, int n, int k, double alpha, double diag,
                  void* stream);
 

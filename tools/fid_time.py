@@ -7,7 +7,8 @@ N = 1000 and 5000:
     Newton-Schulz square roots on `cdf_gemm_f64`), the trace read of every step and the final host read included.
 
 Both are wall-timed around a device synchronisation: medians of the repetitions after the warm-ups (the host route is seconds per call,
-so it gets few).  The two kernels are also event-timed alone: `cdf_moments_f64` at n = 50, d = 2048 and `cdf_gemm_f64` at 2048^3.
+so it gets few).  The kernels are also event-timed alone: `cdf_moments_f64` at n = 50, d = 2048, `cdf_moments_merge_f64` at d = 2048
+(`FidStats.merge` of two accumulators on different pivots) and `cdf_gemm_f64` at 2048^3.  `--kernels-only` stops after those.
 
     python tools/fid_time.py [--out profiles/fid_device.md] [--host-reps 3] [--reps 5] [--sizes 1000,5000]
 
@@ -73,6 +74,7 @@ def main():
     ap.add_argument("--host-reps", type=int, default=3)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--sizes", default="1000,5000")
+    ap.add_argument("--kernels-only", action="store_true", help="time the kernels alone, print the JSON line and leave --out as it is")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "fid_time.py measures on the MI355X; a CPU run cannot give a time"
     from colddiff import metrics
@@ -84,12 +86,19 @@ def main():
     st = metrics.FidStats(D, dev).add(x)
     res["moments_50x2048"] = events(lambda: st.add(x))
     res["moments_50x2048"].update(flop=2 * 50 * D * D // 2, bytes=D * (D + 64) // 2 * 16 + 50 * D * 4)
+    # the merge: b's triangle and a's are read, a's is written (3 x the triangle's tiles; the pivots and sums are 48 KB)
+    other = metrics.FidStats(D, dev).add(features(50, 2, 0.25, dev))
+    res["merge_2048"] = events(lambda: st.merge(other))
+    res["merge_2048"].update(flop=8 * D * (D + 64) // 2, bytes=D * (D + 64) // 2 * 24 + 3 * D * 8)
     A, B, C = (torch.randn(D, D, device=dev, dtype=torch.float64) for _ in range(3))
     res["gemm_2048"] = events(lambda: metrics.gemm_f64(A, B, out=C, alpha=-0.5, diag=1.5), reps=10, warmup=3)
     res["gemm_2048"].update(flop=2 * D ** 3, bytes=3 * D * D * 8)
     res["gemm_2048"]["tflops"] = 2 * D ** 3 / res["gemm_2048"]["median_us"] * 1e-6
-    print("kernels:", res["moments_50x2048"], res["gemm_2048"], flush=True)
+    print("kernels:", res["moments_50x2048"], res["merge_2048"], res["gemm_2048"], flush=True)
     del A, B, C
+    if a.kernels_only:
+        print(json.dumps(res, sort_keys=True))
+        return
 
     for n in (int(v) for v in a.sizes.split(",")):
         fa, fb = features(n, 10, 0.1, dev), features(n, 11, 0.25, dev)
@@ -126,7 +135,7 @@ def main():
         text = open(a.out).read()
         if KEEP in text:
             tail = text[text.index(KEEP):]
-    k, m, gm = res, res["moments_50x2048"], res["gemm_2048"]
+    k, m, gm, mg = res, res["moments_50x2048"], res["gemm_2048"], res["merge_2048"]
     lines = ["# FID metric step: host route against device route", "",
              f"`python tools/fid_time.py` on {k['device']} ({k['cpus']} CPUs for the host route) -- one process, stand-in features [N, 2048] "
              "(two sets per distance), wall time around a device synchronisation, medians after one warm-up.", "",
@@ -144,6 +153,8 @@ def main():
               "| kernel | shape | median | flop | bytes (compulsory) | rate |", "|---|---|---|---|---|---|",
               f"| `cdf_moments_f64` | n = 50, d = 2048 | {m['median_us']:.1f} us | {m['flop'] / 1e9:.2f} G | {m['bytes'] / 1e6:.1f} MB "
               f"(read + write of the triangle's tiles) | {m['bytes'] / m['median_us'] * 1e-6:.2f} TB/s |",
+              f"| `cdf_moments_merge_f64` | d = 2048 | {mg['median_us']:.1f} us | {mg['flop'] / 1e9:.3f} G | {mg['bytes'] / 1e6:.1f} MB "
+              f"(two triangles read, one written) | {mg['bytes'] / mg['median_us'] * 1e-6:.2f} TB/s |",
               f"| `cdf_gemm_f64` | 2048^3 | {gm['median_us'] / 1e3:.2f} ms | {gm['flop'] / 1e9:.1f} G | {gm['bytes'] / 1e6:.1f} MB | {gm['tflops']:.1f} TFLOP/s |", ""]
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:
