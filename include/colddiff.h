@@ -173,7 +173,8 @@ int cdf_nhwc_to_nchw(const float* x, float* y, const float* add, int B, int C, i
  *   v = acc + bias[co] + sbias[b][co]; pre = v; v = act(v) (1 GELU, 2 SiLU, 3 ReLU);
  *   v *= {1: gelu'(mul), 2: silu'(mul), 3: mul}; v += res; accumulate ? y += v : y = v.
  *   batch * batch2 independent GEMMs run in one launch (blockIdx.z = outer*batch2 + inner) with element
- *   strides x_bs / w_bs / y_bs (outer) and x_bs2 / w_bs2 / y_bs2 (inner, e.g. attention heads). */
+ *   strides x_bs / w_bs / y_bs (outer) and x_bs2 / w_bs2 / y_bs2 (inner, e.g. attention heads).
+ *   x (and xa / xb of cdf_conv_wgrad) are read in whole channel quads: the pad channels C .. roundup4(C)-1 must be finite. */
 int cdf_conv_gemm(const float* x, int ldx, const float* w, int ldw, float* y, int ldy, int B, int H, int W, int Cin,
                   int OH, int OW, int Cout, int QH, int QW, int os, int is, int nphase, const int* phase_desc,
                   const float* bias, const float* sbias, int ld_sbias, const float* res, int ldr, float* pre, int ldp,

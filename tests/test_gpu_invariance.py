@@ -245,6 +245,12 @@ for _name, _test in (("cdf_act_fwd", "test_act_past_grid_cap"), ("cdf_act_bwd", 
                      ("cdf_sinusoidal", "test_sinusoidal_past_grid_cap"), ("cdf_linear_small", "test_linear_small_production"),
                      ("cdf_linear_small_wgrad", "test_linear_small_production")):
     COVERED_AT_PRODUCTION_SHAPE[_name].append(_SP + _test)
+# the exact-fp32 GEMM pair: every tile, batched form, epilogue set and slab layout the product launches (test_coverage_guard holds the
+# recordings against that module's form tables)
+_FF = "test_gemm_f32_forms.py::"
+COVERED_AT_PRODUCTION_SHAPE["cdf_conv_gemm"] += [_FF + "test_igemm_single_launch", _FF + "test_igemm_batched_call_sites"]
+COVERED_AT_PRODUCTION_SHAPE["cdf_conv_gemm_io"] += [_FF + "test_igemm_single_launch", _FF + "test_igemm_batched_call_sites"]
+COVERED_AT_PRODUCTION_SHAPE["cdf_conv_wgrad"] += [_FF + "test_wgrad_tiles_plans_splits", _FF + "test_wgrad_batched_and_head_split"]
 # entry points with nothing shape-dependent to test at scale, with the reason
 EXEMPT = {
     "cdf_last_error": "host-side error string",
@@ -261,6 +267,7 @@ EXEMPT = {
 
 
 _GEMM_FAMILY = ("cdf_conv_gemm_bf16x", "cdf_conv_gemm_bf16x_io", "cdf_conv_gemm_bf16x_lnbwd", "cdf_conv_wgrad_bf16x", "cdf_conv_wgrad")
+_F32_GEMM = ("cdf_conv_gemm", "cdf_conv_gemm_io")            # the exact-fp32 pair: guarded form by form too (test_gemm_f32_forms.py)
 
 
 def _guard_calls(bench_data):
@@ -273,7 +280,7 @@ def _guard_calls(bench_data):
 
     def keep(src, rec):
         for n, a in rec.calls:
-            if n in _GEMM_FAMILY:
+            if n in _GEMM_FAMILY or n in _F32_GEMM:
                 gemm.append((src, n, tuple(tuple(v) if hasattr(v, "_length_") else v for v in a)))
     for mode in ("bf16x3", "bf16"):
         with rt.precision_scope(mode), Recorder(rt.lib()) as rec:
@@ -321,7 +328,9 @@ def test_coverage_guard(bench_data):
     The pre-split GEMM family is guarded kernel form by kernel form, not by entry-point name: every (form code, NS) that the bench step,
     the sampler step and config 2's network reach -- asked of the library's own dispatcher (cdf_conv_gemm_bf16x_form /
     cdf_conv_wgrad_bf16x_form) with the recorded arguments -- must be a form some test_gemm_production.BENCH_GEMM / BENCH_WGRAD row resolves
-    to, and every committed row must still be a call the recordings contain."""
+    to, and every committed row must still be a call the recordings contain.  The exact-fp32 pair (cdf_conv_gemm, cdf_conv_gemm_io,
+    cdf_conv_wgrad) likewise: every form (test_gemm_f32_forms.f32_gemm_form / f32_wgrad_form of the recorded arguments) must be one a row
+    of that module's case tables has, and the forms it flags as reached must still be reached."""
     import os
     import re
     from test_kernels_production import BENCH_UNPACK
@@ -345,7 +354,7 @@ def test_coverage_guard(bench_data):
         if name == "cdf_conv_wgrad_bf16x":
             reached_w.setdefault((_wgrad_code(L, name, a), 3 if a[1] else 1), (src, a[9:21], a[22]))
             rows_w.add(gp.wgrad_row(name, a))
-        elif name != "cdf_conv_wgrad":
+        elif name != "cdf_conv_wgrad" and name not in _F32_GEMM:
             reached_g.setdefault((_gemm_code(L, name, a), 3 if a[1] else 1), (src, name, a[9:21]))
             rows_g.add(gp.gemm_row(name, a))
     assert all(c > 0 for c, _ in list(reached_g) + list(reached_w)), (reached_g, reached_w)
@@ -361,3 +370,21 @@ def test_coverage_guard(bench_data):
     resident = [(r, gp.gemm_form(L, r, rt.tune_ptr())[1:]) for r in gp.BENCH_GEMM if gp.decode(gp.gemm_form(L, r, rt.tune_ptr())[0])["form"] == gp.ROWHALO]
     print("resident row-halo rows (tiles, grid):", resident)
     assert any(t > g for _, (t, g) in resident), "no BENCH_GEMM row walks several tiles per resident block"
+    # ---- the exact-fp32 pair (conv_igemm_kernel, conv_wgrad_kernel), form by form: the forms are pure functions of the recorded arguments
+    import test_gemm_f32_forms as ff
+    reached_fg, reached_fw = {}, {}
+    for src, name, a in gemm:
+        if name in _F32_GEMM:
+            reached_fg.setdefault(ff.f32_gemm_form(name, a), (src, name, a[6:18], a[32:40]))
+        elif name == "cdf_conv_wgrad":
+            reached_fw.setdefault(ff.f32_wgrad_form(a), (src, a[6:18], a[19:24]))
+    assert reached_fg and reached_fw
+    for what, reached, tested, flagged in (("GEMM", reached_fg, ff.forms_of_gemm_rows(), ff.REACHED_GEMM),
+                                           ("weight-gradient", reached_fw, ff.forms_of_wgrad_rows(), ff.REACHED_WGRAD)):
+        print("exact-fp32 %s forms reached:" % what)
+        for k in sorted(reached, key=repr):
+            print("    %r," % (k,))
+        untested = {k: v for k, v in reached.items() if k not in tested}
+        assert not untested, "exact-fp32 %s forms the product reaches without a test_gemm_f32_forms row: %s" % (what, untested)
+        stale = sorted(flagged - set(reached), key=repr)
+        assert not stale, "test_gemm_f32_forms flags %s forms as reached that the recordings no longer contain: %s" % (what, stale)
