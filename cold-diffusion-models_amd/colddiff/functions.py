@@ -6,8 +6,6 @@ gradients are accumulated by the kernels straight into ``param.grad`` (one flat 
 an ``anchor`` (a dummy scalar that requires grad) first, so its backward also runs when the
 activation input itself does not require grad (the first block sees the image).
 """
-import os
-
 import torch
 
 from . import convdesc as cd
@@ -72,8 +70,6 @@ def conv_forward(x, Cin, weight, bias, kind="conv", stride=1, pad=None, xs=None,
     plan, _, _, Cout, KK = conv_geom(x, weight, kind, stride, pad)
     sfx = _sp_suffix(Cin * KK, Cout)
     wp = ops.packed(weight, ("conv_fwd" if kind == "conv" else "convT_fwd") + sfx)
-    if xs is None and sfx and _ALWAYS_PRESPLIT and rt.precision != "f32" and Cin % 8 == 0 and x.device.type != "meta":
-        xs = ops.split_bf16(x[..., :Cin] if x.shape[-1] != Cin else x)     # every bf16x3 GEMM goes through the LDS-DMA kernel
     if xs is not None and sfx:
         return ops.conv_gemm_presplit(plan, xs, Cin, wp, Cout, bias=bias, split_out=split_out, planes_only=planes_only, **epi)
     y = ops.conv_gemm(plan, x, Cin, wp, Cout, bias=bias, **epi)
@@ -86,20 +82,19 @@ def want_presplit(Cin, Cout, k):
     return rt.precision != "f32" and Cin % 8 == 0 and Cout % 8 == 0 and bool(_sp_suffix(Cin * k * k, Cout)) and bool(_sp_suffix(Cout * k * k, Cin))
 
 
-_CIN4 = os.environ.get("CDF_CIN4", "1") != "0"    # direct kernels for the <= 4-input-channel image-side convs
-_CIN_DGRAD2 = os.environ.get("CDF_CIN_DGRAD2", "1") != "0"   # their 3x3 data gradient in two stages (ops.conv_cin_dgrad2)
-_ATTN_FUSED = int(os.environ.get("CDF_ATTN_FUSED", "1"))    # to_out folded into the linear-attention product (ops.linattn_project): 0 never, 1 where dim <= heads*32, 2 always
-_LEAN = os.environ.get("CDF_LEAN", "1") != "0"    # skip fp32 copies of tensors only ever consumed as bf16 planes
 _LINEAR_SMALL_M = 256      # batch sizes up to this use the skinny-linear kernels
-_ALWAYS_PRESPLIT = os.environ.get("CDF_ALWAYS_PRESPLIT", "0") != "0"
-_PRESPLIT_1X1 = os.environ.get("CDF_PRESPLIT_1X1", "0") != "0"
-_AUTO_PRESPLIT = os.environ.get("CDF_AUTO_PRESPLIT", "1") != "0"
-_SP_KMIN = int(os.environ.get("CDF_SP_KMIN", "64"))     # tuning knob: smallest K routed to the bf16 matrix cores
-_LN_FUSE = os.environ.get("CDF_LN_FUSE", "1") != "0"  # conv1's data gradient runs the LayerNorm backward in its epilogue (ops.conv_dgrad_lnbwd)
-_PRE_GRAD = os.environ.get("CDF_PRE_GRAD", "0") != "0"  # conv1's epilogue stores GELU'(pre) (same erf / exp evaluation as GELU); conv2's data gradient multiplies by it
-_KV_PLANES = os.environ.get("CDF_KV_PLANES", "1") != "0"     # the k | v projection's backward on operand planes (kv_planes_ok)
-_ATTN_QFOLD = os.environ.get("CDF_ATTN_QFOLD", "1") != "0"   # q projection folded into the attention product too (dim <= heads*32)
-_ATTN_KVCTX = os.environ.get("CDF_ATTN_KVCTX", "1") != "0"   # ... with the k|v projection and the context in one kernel (ops.linattn_kvctx)
+_SP_KMIN = 64              # smallest K routed to the bf16 matrix cores
+# Test / tool seams: plain attributes that a test or tool sets to run an alternative form against the default one.
+_ATTN_FUSED = 1      # to_out folded into the linear-attention product (ops.linattn_project): 0 never, 1 where dim <= heads*32, 2 always (test_modules.py, tools/call_trace.py)
+_ATTN_QFOLD = True   # q projection folded into the attention product too (dim <= heads*32) (test_modules.py, tools/call_trace.py)
+_LEAN = True         # skip fp32 copies of tensors only ever consumed as bf16 planes (test_modules.py)
+_PRE_GRAD = False    # conv1's epilogue stores GELU'(pre) (same erf / exp evaluation as GELU); conv2's data gradient multiplies by it (test_bf16_storage.py)
+
+
+def _lean(pixels):
+    """When every consumer of a tensor reads its bf16 planes (fwd / dgrad GEMMs always, the wgrad GEMM from ops.WGRAD_SP_MIN_M pixels up),
+    its fp32 copy is not written at all."""
+    return _LEAN and pixels >= ops.WGRAD_SP_MIN_M
 
 
 def _sp_suffix(K, N):
@@ -120,10 +115,8 @@ def conv_backward(x, Cin, dy, weight, bias, kind="conv", stride=1, pad=None, nee
         return None
     sfx = _sp_suffix(Cout * KK, Cin)
     wd = ops.packed(weight, ("conv_dgrad" if kind == "conv" else "convT_dgrad") + sfx)
-    if dys is None and sfx and _ALWAYS_PRESPLIT and rt.precision != "f32" and Cout % 8 == 0 and dy.device.type != "meta":
-        dys = ops.split_bf16(dy[..., :Cout] if dy.shape[-1] != Cout else dy)
     if dys is not None and sfx:
-        if (ln is not None and _LN_FUSE and kind == "conv" and dx is None and mul is None and not split_dx and dys[1] is not None
+        if (ln is not None and kind == "conv" and dx is None and mul is None and not split_dx and dys[1] is not None
                 and ops.conv_dgrad_lnbwd_ok(pd, x.shape[0], Cout, Cin)):
             h, norm, mean, rstd = ln
             return ops.conv_dgrad_lnbwd(pd, dys, Cout, wd, Cin, h, norm.g, norm.b, mean, rstd), True
@@ -174,7 +167,7 @@ class CatBuf:
     """The buffer of a skip concatenation torch.cat((x, h), dim=1) (DEBLUR:274), allocated when the SKIP half is produced on the down
     path: the attention block writes h straight into channels [Cx, Cx + Ch) and, on the up path, the producer of x (mid_block2 or the
     transposed-conv upsampler) writes into channels [0, Cx) -- every kernel takes a pixel pitch, so neither half is ever copied
-    (the round-1 `Concat` node spent two cdf_axpby passes per stage on it).  Not a tensor: autograd does not look inside."""
+    (a copying concatenation would spend two cdf_axpby passes per stage on it).  Not a tensor: autograd does not look inside."""
 
     def __init__(self, ref, B, H, W, Cx, Ch, dtype=torch.float32):
         self.Cx, self.Ch = Cx, Ch
@@ -202,26 +195,6 @@ class Join(torch.autograd.Function):
     @staticmethod
     def backward(ctx, d):
         return d[..., :ctx.Ca], d[..., ctx.Ca:], None
-
-
-class Concat(torch.autograd.Function):
-    """torch.cat((a, b), dim=channel) on NHWC maps; the backward hands out channel-slice views."""
-
-    @staticmethod
-    def forward(ctx, a, b):
-        B, H, W, Ca = a.shape
-        Cb = b.shape[-1]
-        ctx.Ca = Ca
-        out = torch.empty((B, H, W, Ca + Cb), device=a.device, dtype=torch.float32)
-        L, S = rt.lib(), rt.stream(a)
-        rows = B * H * W
-        L.cdf_axpby(P(out), Ca + Cb, P(a), ops.ld_of(a), rows, Ca, 0.0, 1.0, S)
-        L.cdf_axpby(P(out) + 4 * Ca, Ca + Cb, P(b), ops.ld_of(b), rows, Cb, 0.0, 1.0, S)
-        return out
-
-    @staticmethod
-    def backward(ctx, d):
-        return d[..., :ctx.Ca], d[..., ctx.Ca:]
 
 
 class Sinusoidal(torch.autograd.Function):
@@ -410,7 +383,7 @@ class ConvFn(torch.autograd.Function):
         Cout = mod.weight.shape[0] if kind == "conv" else mod.weight.shape[1]
         # 4x4 stride-2 down / transposed up-sampling convs: every input pixel feeds several taps and N tiles, and the
         # same planes serve the weight gradient -> split once, use the LDS-DMA kernels (1x1 convs read x once: not worth it)
-        xs = ops.split_bf16(x) if (_AUTO_PRESPLIT and (k > 1 or _PRESPLIT_1X1) and want_presplit(Cin, Cout, k)) else None
+        xs = ops.split_bf16(x) if (k > 1 and want_presplit(Cin, Cout, k)) else None
         # dest: a CatBuf (the conv writes its first half) or the destination view itself (a skip tensor written into its second half)
         ydst = dest.first() if isinstance(dest, CatBuf) else dest
         y = conv_forward(x, Cin, mod.weight, mod.bias, kind, stride, pad, xs=xs, **({"y": ydst} if ydst is not None else {}))
@@ -448,9 +421,7 @@ class ConvNextBlockFn(torch.autograd.Function):
         # operands that feed several GEMMs (fwd now, dgrad/wgrad later, every N tile) are split into bf16 hi/lo ONCE, by
         # the kernel that produces them (LayerNorm, the GELU epilogue of conv1, the GELU' epilogue of conv2's dgrad)
         sp1, sp2 = want_presplit(dim, mid, 3), want_presplit(mid, dim_out, 3)
-        # When every consumer of a tensor reads its bf16 planes (fwd / dgrad GEMMs always, the wgrad GEMM from ops.WGRAD_SP_MIN_M
-        # pixels up), its fp32 copy is not written at all: LN output, GELU output, conv2's data gradient.
-        lean = _LEAN and B * H * W >= ops.WGRAD_SP_MIN_M
+        lean = _lean(B * H * W)             # no fp32 copy of the LN output, the GELU output, conv2's data gradient
         hn_s = None
         if m.has_norm:
             if sp1:
@@ -463,7 +434,7 @@ class ConvNextBlockFn(torch.autograd.Function):
             hn_s = ops.split_bf16(hn) if sp1 else None
         pre = ops.new_feat(x, B, H, W, mid) if grad_on else None
         # image-side block (dim <= 4 input channels): direct vector-ALU convolutions instead of K <= 36 GEMMs
-        ctx.cin4 = _CIN4 and ops.cin4_ok(hn, dim, c1.weight) and ops.cin4_ok(x, dim, c1.weight)
+        ctx.cin4 = ops.cin4_ok(hn, dim, c1.weight) and ops.cin4_ok(x, dim, c1.weight)
         ctx.pre_grad = False
         if ctx.cin4:
             if sp2:
@@ -477,7 +448,7 @@ class ConvNextBlockFn(torch.autograd.Function):
                                   **({"pre_grad": True} if ctx.pre_grad else {}))
         else:
             a, a_s = conv_forward(hn, dim, c1.weight, c1.bias, act=ACT_GELU, pre=pre, xs=hn_s), None
-        ctx.res4 = bool(m.has_res_conv and _CIN4 and ops.cin4_ok(x, dim, m.res_conv.weight))
+        ctx.res4 = bool(m.has_res_conv and ops.cin4_ok(x, dim, m.res_conv.weight))
         if ctx.res4:
             res = ops.conv_cin4_fwd(x, m.res_conv.weight, m.res_conv.bias)
         elif m.has_res_conv:
@@ -518,7 +489,7 @@ class ConvNextBlockFn(torch.autograd.Function):
         # conv2 -> (fused GELU') -> conv1
         do_s = ops.split_or_planes(do) if a_s is not None else None       # (planes written by the producer of `do`, else cdf_split_bf16)
         if hn_s is not None:
-            lean = _LEAN and a_s is not None and a.shape[0] * a.shape[1] * a.shape[2] >= ops.WGRAD_SP_MIN_M
+            lean = a_s is not None and _lean(a.shape[0] * a.shape[1] * a.shape[2])
             dpre, dpre_s = conv_backward(a, mid, do, c2.weight, c2.bias, mul=pre, mul_mode=3 if ctx.pre_grad else 1, xs=a_s, dys=do_s, split_dx=True,
                                          planes_only=lean)
         else:
@@ -527,13 +498,9 @@ class ConvNextBlockFn(torch.autograd.Function):
         if ctx.cin4:
             # weight / bias gradient by the direct kernel (reads dpre once); the data gradient in two stages (sum over the mid
             # channels per pixel as a 1x1 GEMM, then the nine shifted 3-vectors: ops.conv_cin_dgrad2) instead of a K = 9 mid
-            # gather-GEMM with 3 useful output columns (0.4 ms at 128 x 128)
+            # gather-GEMM with 3 useful output columns (0.4 ms at 128 x 128).  (c1 is 3 x 3: the block's own constructor.)
             ops.conv_cin4_bwd(hn, dpre, c1.weight, c1.bias, False)
-            if _CIN_DGRAD2 and c1.weight.shape[-1] == 3:
-                dhn = ops.conv_cin_dgrad2(dpre, mid, c1.weight)
-            else:
-                pd = _conv_plans("conv", hn.shape[1], hn.shape[2], 3, 1, (1, 1, 1, 1))[1]
-                dhn = ops.conv_gemm(pd, dpre, mid, ops.packed(c1.weight, "conv_dgrad"), dim)
+            dhn = ops.conv_cin_dgrad2(dpre, mid, c1.weight)
         else:
             dhn = conv_backward(hn, dim, dpre, c1.weight, c1.bias, xs=hn_s, dys=dpre_s, ln=(h, m.net[0], mean, rstd) if m.has_norm else None)
             if m.has_norm:
@@ -574,7 +541,7 @@ def kv_planes_ok(xn, dim, heads):
     gradient are the LDS-DMA plane GEMMs instead of the in-kernel-split / exact-fp32 kernels reading 1 GB of fp32 dk | dv each at
     128 x 128 (0.53 + 0.41 ms per step there)."""
     B, H, W, _ = xn.shape
-    return (_KV_PLANES and rt.precision != "f32" and heads <= 4 and dim % 8 == 0 and dim >= 64 and B * H * W >= ops.WGRAD_SP_MIN_M
+    return (rt.precision != "f32" and heads <= 4 and dim % 8 == 0 and dim >= 64 and B * H * W >= ops.WGRAD_SP_MIN_M
             and xn.device.type != "meta")
 
 
@@ -603,7 +570,7 @@ def linattn_block_forward(ctx, x, m, dest, bf):
     if ctx.qfold:
         # q folded in as well: only k | v are projected, y = xn . N_b + b + x (ops.linattn_fold; on the bf16 stream the product reads the
         # residual from it and writes its result into it: x and y cross the boundary once each, as bf16)
-        if _ATTN_KVCTX and ops.linattn_kvctx_ok(xn, dim, att.heads):
+        if ops.linattn_kvctx_ok(xn, dim, att.heads):
             kv, cx, cxs, kmax, ksum = ops.linattn_kvctx(xn, dim, w_qkv, att.heads, att.scale)    # one pass: k | v never re-read
         else:
             plan = _conv_plans("conv", xn.shape[1], xn.shape[2], 1, 1, (0, 0, 0, 0))[0]        # the k | v rows of to_qkv as a 1x1 conv of their own
@@ -742,7 +709,7 @@ class UpsampleConvFn(torch.autograd.Function):
     def forward(ctx, anchor, x, conv, out=None):
         up = ops.upsample2(x)
         C = x.shape[-1]
-        ctx.sp = _AUTO_PRESPLIT and want_presplit(C, conv.weight.shape[0], 3)
+        ctx.sp = want_presplit(C, conv.weight.shape[0], 3)
         y = conv_forward(up, C, conv.weight, conv.bias, xs=ops.split_bf16(up) if ctx.sp else None, **({"y": out} if out is not None else {}))
         ctx.conv = conv
         _used(ctx, conv)
@@ -766,12 +733,12 @@ class ResnetBlockFn(torch.autograd.Function):
     def forward(ctx, anchor, x, tbias, m, out=None):
         cin, cout = m.in_channels, m.out_channels
         # the 3x3 convs' operands are split into bf16 hi/lo planes once (forward, data gradient and weight gradient read them)
-        sp1 = _AUTO_PRESPLIT and want_presplit(cin, cout, 3)
-        sp2 = _AUTO_PRESPLIT and want_presplit(cout, cout, 3)
+        sp1 = want_presplit(cin, cout, 3)
+        sp2 = want_presplit(cout, cout, 3)
         # GroupNorm + SiLU (+ dropout) write the next conv's bf16 operand planes themselves; when every consumer reads the planes
         # (fwd / dgrad GEMMs always, the weight-gradient GEMM from ops.WGRAD_SP_MIN_M pixels up) the fp32 copy is not written at all
         B, H, W, _ = x.shape
-        lean = _LEAN and B * H * W >= ops.WGRAD_SP_MIN_M
+        lean = _lean(B * H * W)
         if sp1:
             h1, mean1, rstd1, h1_s = ops.groupnorm_fwd(x, m.norm1.weight, m.norm1.bias, GN_GROUPS, GN_EPS, True, split_out=True, planes_only=lean)
         else:

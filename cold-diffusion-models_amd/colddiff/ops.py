@@ -4,7 +4,6 @@ Feature maps are NHWC views ``[B, H, W, C]`` with unit channel stride and an arb
 (``t.stride(-2)``), so a channel slice of a wider buffer is a valid operand.  Tensors whose logical
 channel count is not a multiple of 4 are stored padded to 4 with zero pad channels.
 """
-import os
 import weakref
 
 import torch
@@ -44,12 +43,11 @@ def new_feat(ref, B, H, W, C, zero=False):
 # ---------------------------------------------------------------------------------------------------
 _pack_cache = {}          # (id(param), kind) -> _Packed
 _pack_tables = {}         # device -> (signature, device table tensor, nentries, nblocks): the cdf_pack_many descriptor table
-_PACK_ALL = os.environ.get("CDF_PACK_ALL", "1") != "0"
 # smallest pixel count whose weight gradient runs on the bf16 matrix cores (below, the fp32-MFMA kernel; 2048 until the end of round 2:
 # the 4 x 4-pixel level of the 32 x 32 configurations is M = 512 with 512 -> 1024 channels, 62 -> 28 us per launch)
-WGRAD_SP_MIN_M = int(os.environ.get("CDF_WGRAD_SP_MIN_M", "512"))
-_SP_WGRAD_MIN_PIX = int(os.environ.get("CDF_SP_WGRAD_MIN_PIX", "128"))   # smallest pixel count per split of the in-kernel-split weight gradient
-_ATTN_KV_FUSED = os.environ.get("CDF_ATTN_KV_FUSED", "1") != "0"    # one-kernel k / v attention backward (k_attn.hip)
+WGRAD_SP_MIN_M = 512
+_SP_WGRAD_MIN_PIX = 128   # smallest pixel count per split of the in-kernel-split weight gradient
+_ATTN_KV_FUSED = True     # one-kernel k / v attention backward (k_attn.hip).  Test / tool seam: test_kernels_production.py, tools/call_trace.py
 
 
 class _Packed:
@@ -189,7 +187,7 @@ def packed(param, kind):
     if hit is not None and hit.ref() is not param:           # the weakref guards against id()/address reuse by a new tensor
         hit = None
     if hit is not None and hit.ptr == param.data_ptr() and hit.version == param._version and hit.precision == rt.precision:
-        if hit.epoch != epoch and _PACK_ALL and hit.geom is not None and param.device.type != "meta" and hit.last_used == hit.epoch:
+        if hit.epoch != epoch and hit.geom is not None and param.device.type != "meta" and hit.last_used == hit.epoch:
             _repack_all(param.device, hit.epoch)             # (moves hit.epoch to this epoch if it refreshed this layout too)
         if hit.epoch == epoch:
             hit.last_used = epoch
@@ -248,7 +246,10 @@ def split_bf16(x):
 # A backward kernel whose result feeds the next block's GEMMs can write it as bf16 planes too (cdf_dwconv7_planes, cdf_layernorm_c_bwd_planes):
 # the planes ride on the gradient tensor through the autograd engine (`_cdf_planes`, with the tensor's version counter -- the engine sums
 # gradients IN PLACE when a tensor has several consumers, which bumps it) and the consumer takes them instead of launching cdf_split_bf16.
-GRAD_PLANES = os.environ.get("CDF_GRAD_PLANES", "1") != "0"
+# The C API writes through raw pointers and does not bump Tensor._version, so the version guard only sees writes made through torch.  Hence:
+# planes are attached only to a tensor that the attaching op itself just produced, and every op that writes into a caller-supplied
+# output (conv_gemm* with y=, dwconv7 with y= / accumulate, layernorm_bwd with dx=) drops a stale record from it first (drop_planes).
+GRAD_PLANES = True        # test seam: test_modules.py runs the net with and without gradient planes
 
 
 def want_grad_planes(C):
@@ -258,6 +259,12 @@ def want_grad_planes(C):
 def attach_planes(t, planes):
     t._cdf_planes = (planes, t._version)
     return t
+
+
+def drop_planes(t):
+    """A kernel is about to write into t: planes attached to it no longer describe it."""
+    if hasattr(t, "_cdf_planes"):
+        del t._cdf_planes
 
 
 def grad_planes(t):
@@ -323,6 +330,8 @@ def conv_gemm_presplit(plan, xs, Cin, wp, Cout, y=None, bias=None, sbias=None, r
     ys = split_planes_like(hi, B, plan.OH, plan.OW, Cout) if (split_out and Cout % 4 == 0) else None
     if y is None:
         y = shape_only(B, plan.OH, plan.OW, Cout) if planes_only else new_feat(hi, B, plan.OH, plan.OW, Cout)
+    else:
+        drop_planes(y)
     assert not pre_grad or (pre is not None and act in (1, 2))
     _gemm_bf16x(plan, hi, lo, hi.shape[-1], wp, Cin, Cout, y, ld_of(y), ys or (None, None), ys[0].shape[-1] if ys else 0,
                 bias, sbias, res, pre, mul, act, mul_mode, accumulate, IO_PRE_GRAD if pre_grad else None)
@@ -414,6 +423,8 @@ def conv_gemm(plan, x, Cin, wp, Cout, y=None, bias=None, sbias=None, res=None, p
     B = x.shape[0]
     if y is None:
         y = new_feat(x, B, plan.OH, plan.OW, Cout)
+    else:
+        drop_planes(y)
     ldv = lambda t: 0 if t is None else ld_of(t)
     if isinstance(wp, tuple):                     # (hi, lo) bf16 planes -> split-precision kernel
         hi, lo = wp
@@ -558,6 +569,8 @@ def layernorm_bwd(dy, x, g_param, b_param, mean, rstd, dx=None, add=None, planes
     assert not (acc and add is not None)
     if dx is None:
         dx = torch.empty((B, H, W, C), device=x.device, dtype=torch.float32)
+    else:
+        drop_planes(dx)
     part = torch.empty((L.cdf_layernorm_blocks(M, C) * 2 * C,), device=x.device, dtype=torch.float32)
     if planes and C % 8 == 0 and dx.is_contiguous():
         ps = split_planes_like(x, B, H, W, C)
@@ -575,6 +588,8 @@ def dwconv7(x, wp, bias, sbias, flip=0, y=None, accumulate=0, res=None, planes=F
     B, H, W, Cp = x.shape
     if y is None:
         y = torch.empty((B, H, W, Cp), device=x.device, dtype=torch.float32)
+    else:
+        drop_planes(y)
     if planes and Cp % 8 == 0 and y.is_contiguous():
         ps = split_planes_like(x, B, H, W, Cp)
         rt.lib().cdf_dwconv7_planes(P(x), ld_of(x), P(wp), wp.shape[-1], P(bias), P(sbias), 0 if sbias is None else sbias.stride(0), P(y),

@@ -41,8 +41,8 @@ class _Anchor(nn.Module):
         return a
 
 
-_CONCAT_FREE = __import__("os").environ.get("CDF_CONCAT_FREE", "1") != "0"
-_TIME_BIAS_ALL = __import__("os").environ.get("CDF_TIME_BIAS_ALL", "1") != "0"     # one launch for every block's time-bias Linear
+# one launch for every block's time-bias Linear.  Tool seam (no environment read): tools/sample_prof.py times the per-block form against it
+_TIME_BIAS_ALL = True
 
 
 def anchor(t):
@@ -232,7 +232,7 @@ class Unet(nn.Module):
         T = lambda blk: tbs.get(id(blk))
         # bf16 activation storage ("bf16" arithmetic mode): the stream between blocks, every saved activation and every GEMM input is ONE
         # bf16 plane from the output of the image-side block to the input of the 3-channel output conv (colddiff/bf16store.py)
-        bfs = BFS.enabled() and _CONCAT_FREE and self._bf16_ok()
+        bfs = BFS.enabled() and self._bf16_ok()
         conv = (lambda *a_: BFS.ConvFnBF.apply(*a_)) if bfs else (lambda *a_: F_.ConvFn.apply(*a_))
         h = []
         for lvl, (convnext, convnext2, attn, downsample) in enumerate(self.downs):
@@ -243,7 +243,7 @@ class Unet(nn.Module):
             else:
                 x = convnext2(x, gt, tb=T(convnext2))
             cat = None
-            if _CONCAT_FREE and lvl >= len(self.downs) - nskip:
+            if lvl >= len(self.downs) - nskip:
                 B_, H_, W_, C_ = x.shape
                 cat = F_.CatBuf(x, B_, H_, W_, C_, C_, dtype=x.dtype)
             x = attn(x, cat)
@@ -256,11 +256,8 @@ class Unet(nn.Module):
         x = self.mid_block2(x, gt, h[-1][1], tb=T(self.mid_block2))     # (its output is the first half of the deepest concat)
 
         for j, (convnext, convnext2, attn, upsample) in enumerate(self.ups):
-            skip, cat = h.pop()
-            if cat is not None:
-                x = (BFS.JoinBF if bfs else F_.Join).apply(x, skip, cat)
-            else:
-                x = F_.Concat.apply(x, skip)
+            skip, cat = h.pop()                                # (every level an up stage consumes has its concat buffer)
+            x = (BFS.JoinBF if bfs else F_.Join).apply(x, skip, cat)
             x = convnext(x, gt, tb=T(convnext))
             x = convnext2(x, gt, tb=T(convnext2))
             x = attn(x)

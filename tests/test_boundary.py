@@ -140,3 +140,18 @@ def test_reference_driver_call_is_accepted(tmp_path):
                                                 attn_resolutions=(16,), dropout=0.1)
     for name in ("train", "save", "load", "test_from_data"):
         assert callable(getattr(mine.Trainer, name))
+
+
+def test_package_reads_no_cdf_environment_variable():
+    """The package's behaviour depends on its arguments, tensor shapes, runtime.precision and the documented COLDDIFF_* variables only: no
+    string literal in it names a CDF_* variable (however the environment is reached: os.environ, os.getenv or an alias of either).  The
+    CDF_* names of the C ABI (CDF_IO_*, CDF_ABI_VERSION) occur in comments and inside a header regex, never at the start of a literal."""
+    import glob
+    import re
+    found = []
+    for path in sorted(glob.glob(os.path.join(PKG, "colddiff", "**", "*.py"), recursive=True)):
+        with open(path) as f:
+            for no, text in enumerate(f, 1):
+                if re.search(r"""["']CDF_""", text):
+                    found.append("%s:%d: %s" % (os.path.relpath(path, PKG), no, text.strip()))
+    assert not found, "CDF_* environment switches in the package:\n" + "\n".join(found)

@@ -1,11 +1,13 @@
 """Time Residual(PreNorm(LinearAttention)) forward + backward at the CelebA-128 levels (B = KB_B, default 32):
    python tools/attnbench.py            # per-level fwd / bwd ms
    rocprofv3 --kernel-trace -d out -- python tools/attnbench.py   # per-kernel table through tools/prof_summary.py
-KB_LEVELS="64-128,128-64" picks (dim-size) pairs."""
+KB_LEVELS="64-128,128-64" picks (dim-size) pairs; CDF_ATTN_FUSED=0/1/2 and CDF_ATTN_QFOLD=0 pick the arithmetic form (read here, set on colddiff.functions)."""
 import os, sys, torch
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(REPO, "cold-diffusion-models_amd"))
-from colddiff import unet as U
+from colddiff import functions as F_, unet as U
+F_._ATTN_FUSED = int(os.environ.get("CDF_ATTN_FUSED", F_._ATTN_FUSED))
+F_._ATTN_QFOLD = os.environ.get("CDF_ATTN_QFOLD", "1") != "0"
 dev = torch.device("cuda:0")
 B = int(os.environ.get("KB_B", "32")); iters = int(os.environ.get("KB_ITERS", "5"))
 levels = [(64, 128), (128, 64), (256, 32), (512, 16)]
