@@ -118,7 +118,7 @@ class GemmTuning:
                 self.set(**{field: v})
         return self
 
-    # the values cdf_tune_ok (csrc/k_conv_sp.hip) accepts, field by field
+    # the values cdf_tune_ok (csrc/cdf_conv_sp.h) accepts, field by field
     _ALLOWED = {"rowhalo_stream": (0, 1), "epilogue": (0, 1), "resident_reserve": range(0, 249), "halo_bm": (0, 128, 256), "max_bm": (0, 128, 256),
                 "tile_bm": (0, 64, 128, 256), "tile_bn": (0, 64, 128), "halo": range(0, 128)}
 

@@ -1,5 +1,5 @@
 """Tap tables that express every dense convolution of the two UNets (forward, data gradient,
-weight gradient) as the one gather-GEMM the HIP library implements (see csrc/k_conv.hip).
+weight gradient) as the one gather-GEMM the HIP library implements (see csrc/k_conv.hip; the descriptors are parsed in csrc/cdf_gemm_args.h).
 
 A *phase descriptor* is the flat int list ``[oy, ox, ntaps, (dy, dx, wi) * ntaps]`` per output
 phase; a *wgrad tap descriptor* is ``(day, dax, dby, dbx) * ntaps``.  Tap index ``wi = ky*KW+kx``.

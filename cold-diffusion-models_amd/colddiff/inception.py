@@ -30,7 +30,7 @@ FID_WEIGHTS_FILE = 'pt_inception-2015-12-05-6726825d.pth'
 ACT_RELU = 3
 
 
-MAX_TAPS = 16          # taps per gather-GEMM launch (CDF_MAX_TAPS in csrc/k_conv.hip)
+MAX_TAPS = 16          # taps per gather-GEMM launch (CDF_MAX_TAPS in csrc/cdf_gemm_args.h)
 
 
 @lru_cache(maxsize=None)

@@ -823,7 +823,7 @@ def linattn_kvctx_ok(xn, dim, heads):
 
 
 def linattn_kvctx(xn, dim, w_qkv, heads, scale):
-    """kv = xn . Wkv^T ([B,H,W,2 HD]) and (ctx, ctxs, kmax, ksum) of LinearAttention in one pass over the pixels (k_conv_sp.hip:
+    """kv = xn . Wkv^T ([B,H,W,2 HD]) and (ctx, ctxs, kmax, ksum) of LinearAttention in one pass over the pixels (k_attn_kvctx.hip:
     linattn_kvctx_kernel): k and v are written once and not read back."""
     L, S = rt.lib(), rt.stream(xn)
     B, H, W, _ = xn.shape

@@ -292,6 +292,11 @@ int cdf_check_launch(const char* what);
     } while (0)
 
 static inline int cdf_cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
+static inline int cdf_ew_grid4k(long long n) {               // blocks of 256 threads for an n-element grid-stride loop, at most 4096
+    long long g = (n + 255) / 256;
+    if (g > 4096) g = 4096;
+    return g < 1 ? 1 : (int)g;
+}
 
 // XCD-aware work order.  Workgroups are handed to the 8 XCDs (each with its own 4 MB L2) round-robin in dispatch order, so
 // work items that are neighbours in memory -- adjacent image tiles with a shared halo, the taps of one pixel range -- land on 8
@@ -302,6 +307,20 @@ __device__ __forceinline__ int cdf_xcd_order(int bid, int nblk) {
     const int xcd = bid & 7, idx = bid >> 3;
     const int base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
     return base + idx;
+}
+
+// ... for the weight-gradient grids (tiles, taps, splits): all tiles and taps of a pixel range run on one XCD at about the same time and share
+// its L2 (in dispatch order each of the 8 L2s fetched the same operand rows: measured 4-6x the algorithmic bytes, rocprofv3 FETCH_SIZE).
+__device__ __forceinline__ void cdf_wgrad_block(int enable, int& bx, int& by, int& bz) {
+    bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
+    if (enable) {
+        const int gx = gridDim.x, gy = gridDim.y;
+        const int v = cdf_xcd_order(bx + gx * (by + gy * bz), gx * gy * (int)gridDim.z);
+        bx = v % gx;
+        const int t2 = v / gx;
+        by = t2 % gy;
+        bz = t2 / gy;
+    }
 }
 
 // ---- device helpers ---------------------------------------------------------------------

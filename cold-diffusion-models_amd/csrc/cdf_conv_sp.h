@@ -1,6 +1,7 @@
 // cdf_conv_sp.h -- what the translation units of the split-precision / bf16 GEMM family share (round 6: k_conv_sp.hip was one 2600-line
 // unit of 104 kernel instantiations, 3 minutes to compile; now one unit per kernel family, compiled in parallel):
-//   k_conv_sp.hip         in-kernel-split GEMM + weight gradient, operand split / widen / weight packing, the k | v + context kernel
+//   k_conv_sp.hip         in-kernel-split GEMM + weight gradient
+//   k_attn_kvctx.hip      the k | v + context kernel of LinearAttention
 //   k_conv_spx.hip        generic pre-split gather-GEMM (LDS-DMA), split-K finish, the dispatcher and the C entry points of the pre-split GEMM
 //   k_conv_halo.hip       3 x 3 stride-1 GEMM with the input tile + halo resident in LDS
 //   k_conv_rowhalo.hip    resident row-halo stream kernel (64 / 128 input channels at 128-pixel width)
@@ -9,11 +10,8 @@
 // forward kernels share (DMA slot, weight row / offset, DMA segments, fragment reads, the de-phased step) and their LDS layouts (SpxLayout,
 // HaloLayout, RowHaloLayout -- read by the kernel AND its launcher).  Accumulator zeroing / row map / staging and CDF_LAUNCH_LDS: cdf_common.h.
 #pragma once
-#include "cdf_common.h"
-#include "cdf_epilogue.h"
+#include "cdf_gemm_args.h"
 #include "colddiff.h"
-
-#define CDF_MAX_TAPS 16
 
 typedef short bf16x8_v __attribute__((ext_vector_type(8)));
 typedef short bf16x4_v __attribute__((ext_vector_type(4)));
@@ -32,18 +30,13 @@ __device__ __forceinline__ bf16x4_v cdf_lds_read_tr16(const unsigned short* p) {
 }
 #endif
 
-struct SpPhase {
-    int oy, ox, ntaps;
-    signed char dy[CDF_MAX_TAPS], dx[CDF_MAX_TAPS], wi[CDF_MAX_TAPS];
-};
-
 // Block tile BM x BN, WM x WN waves of (BM/WM) x (BN/WN): the whole tile goes through LDS in one pass (cdf_epilogue.h).
 constexpr int CDF_SP_CPITCH = 136;
 constexpr size_t CDF_SP_EPI_LDS = (size_t)128 * CDF_SP_CPITCH * sizeof(float);
 
 // BFF: the kernel's epilogue family (cdf_epilogue.h: ids 1..6 for fp32 tensors, 7..11 for bf16 activation storage = the NS == 1 kernels)
 template <int BM, int BN, int WM = 2, int WN = 2, bool BFF = false, class Args>
-__device__ __forceinline__ void cdf_sp_epilogue(const Args& a, const SpPhase& ph, const f32x16_t (&acc)[BM / WM / 32][BN / WN / 32], float* cs,
+__device__ __forceinline__ void cdf_sp_epilogue(const Args& a, const CdfPhase& ph, const f32x16_t (&acc)[BM / WM / 32][BN / WN / 32], float* cs,
                                                 int tile_m, int tile_n, int M, int tid) {
     constexpr int CP = BN + 8, TM = BM / WM, TN = BN / WN, NTHR = 64 * WM * WN;
     const int lane = tid & 63, wave = tid >> 6, wm = wave / WN, wn = wave % WN, half = lane >> 5, l31 = lane & 31;
@@ -97,7 +90,7 @@ struct SpArgs {
     const float* ln_rstd;
     float* ln_part;
     int ld_lnx;
-    SpPhase ph[4];
+    CdfPhase ph[4];
 };
 
 
@@ -115,13 +108,6 @@ __device__ __forceinline__ void cdf_split4_trunc(const float4& v, uint2& hi, uin
     const unsigned r3 = __float_as_uint(v.w - __uint_as_float(u3 & 0xFFFF0000u));
     lo.x = cdf_pack_hi16(r0, r1);
     lo.y = cdf_pack_hi16(r2, r3);
-}
-
-__device__ __forceinline__ int cdf_sp_swizzle(int bid, int nblk) {
-    const int q = nblk >> 3, r = nblk & 7;
-    const int xcd = bid & 7, idx = bid >> 3;
-    const int base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    return base + idx;
 }
 
 // One algorithmic product a * b on the matrix cores.  NS = 3: split precision, al*bh + ah*bl + ah*bh (x = hi + lo bf16 terms,
@@ -284,23 +270,6 @@ struct RowHaloLayout {
     static_assert(bytes <= CDF_LDS_BYTES, "streaming row-halo tile does not fit the LDS");
 };
 
-// XCD-aware block order of the weight-gradient grids (tiles, taps, splits).  Workgroups go to the 8 XCDs round-robin in
-// dispatch order, so the taps of one pixel range (next to each other in dispatch order) would land on 8 different L2s
-// and each of them would fetch the same operand rows over the fabric: measured 4-6x the algorithmic bytes (rocprofv3
-// FETCH_SIZE).  Re-numbered so that every XCD works through a CONTIGUOUS range of (tile, tap, split) ids: all tiles and
-// taps of a pixel range run on one XCD at about the same time and share its L2.
-__device__ __forceinline__ void cdf_wgrad_block(int enable, int& bx, int& by, int& bz) {
-    bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
-    if (enable) {
-        const int gx = gridDim.x, gy = gridDim.y;
-        const int v = cdf_sp_swizzle(bx + gx * (by + gy * bz), gx * gy * (int)gridDim.z);
-        bx = v % gx;
-        const int t2 = v / gx;
-        by = t2 % gy;
-        bz = t2 / gy;
-    }
-}
-
 #define CDF_GLDS16_K(g, l) CDF_GLDS16(g, l)
 
 struct SpxArgs {
@@ -333,7 +302,7 @@ struct SpxArgs {
     const float* ln_rstd;
     float* ln_part;
     int ld_lnx;
-    SpPhase ph[4];
+    CdfPhase ph[4];
 };
 
 // what cdf_epilogue_rows reads, for a raw store of the accumulator tile (split-K partial sums): rows m of a [M][ldy] slab

@@ -400,7 +400,7 @@ extern "C" int cdf_linattn_context(const float* qkv, int ld, int koff, float* ct
 }
 
 // Fold of nparts context partials per image and head (layout of cdf_linattn_context's workspace with nsplit = nparts:
-// max [B][nparts][HD] | ctx [B][nparts][heads][32][32] | sum [B][nparts][HD]) as written by cdf_linattn_kvctx (k_conv_sp.hip).
+// max [B][nparts][HD] | ctx [B][nparts][heads][32][32] | sum [B][nparts][HD]) as written by cdf_linattn_kvctx (k_attn_kvctx.hip).
 extern "C" int cdf_linattn_finalize(const float* ws, int nparts, float* ctx, float* ctxs, float* kmax, float* ksum, int B, int heads,
                                     float scale, void* stream) {
     CDF_REQUIRE(ws && ctx && ctxs && kmax && ksum && nparts >= 1 && nparts <= 1024 && B > 0 && heads >= 1, "cdf_linattn_finalize: bad args");

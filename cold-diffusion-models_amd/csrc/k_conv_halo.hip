@@ -48,9 +48,9 @@ __global__ void __launch_bounds__(512, 1) conv_igemm_halo_kernel(SpxArgs a) {
     const int wm = wave / WN, wn = wave % WN;
     const int M = a.B * a.QH * a.QW;
     const int tiles_n = (a.Cout + BN - 1) / BN, tiles_m = M / BM;
-    const int tile = cdf_sp_swizzle(blockIdx.x, tiles_m * tiles_n);
+    const int tile = cdf_xcd_order(blockIdx.x, tiles_m * tiles_n);
     const int tile_m = tile / tiles_n, tile_n = tile - tile_m * tiles_n;
-    const SpPhase& ph = a.ph[0];
+    const CdfPhase& ph = a.ph[0];
     const int tpi = a.H / TH;                                              // tiles per image
     const int img = tile_m / tpi, y0 = (tile_m - img * tpi) * TH;
 

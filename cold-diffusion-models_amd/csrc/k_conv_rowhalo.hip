@@ -47,7 +47,7 @@ __global__ void __launch_bounds__(512, 1) conv_igemm_rowhalo_stream_kernel(SpxAr
     const int wm = wave / WN, wn = wave % WN;
     const int M = a.B * a.QH * a.QW;
     const int tiles_n = (a.Cout + BN - 1) / BN, tiles_m = M / BM, ntiles = tiles_m * tiles_n;
-    const SpPhase& ph = a.ph[0];
+    const CdfPhase& ph = a.ph[0];
     const int tpi = a.H / TH;
 
     const int srow = cdf_dma_row(lane), q8 = cdf_dma_col(lane);
@@ -97,7 +97,7 @@ __global__ void __launch_bounds__(512, 1) conv_igemm_rowhalo_stream_kernel(SpxAr
 
     auto tile_pos = [&](int v, int& img, int& y0, int& tn, int& tm) {    // virtual block id -> tile (img < 0: past the last tile)
         if (v < ntiles) {
-            const int tile = cdf_sp_swizzle(v, ntiles);
+            const int tile = cdf_xcd_order(v, ntiles);
             tm = tile / tiles_n;
             tn = tile - tm * tiles_n;
             img = tm / tpi;

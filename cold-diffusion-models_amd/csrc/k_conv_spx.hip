@@ -28,9 +28,9 @@ __global__ void __launch_bounds__(64 * WM * WN, OCC) conv_igemm_spx_kernel(SpxAr
     const int wm = wave / WN, wn = wave % WN;
     const int M = a.B * a.QH * a.QW;
     const int tiles_n = (a.Cout + BN - 1) / BN, tiles_m = (M + BM - 1) / BM;
-    const int tile = cdf_sp_swizzle(blockIdx.x, tiles_m * tiles_n);
+    const int tile = cdf_xcd_order(blockIdx.x, tiles_m * tiles_n);
     const int tile_m = tile / tiles_n, tile_n = tile - tile_m * tiles_n;
-    const SpPhase& ph = a.ph[blockIdx.y];
+    const CdfPhase& ph = a.ph[blockIdx.y];
 
     // DMA slots of this lane: wave w fills the 16-row segments w*SA + p of both A planes and w*SB + p of both B planes;
     // inside a segment lane l is row l >> 2, LDS column l & 3, i.e. global column (l & 3) ^ ((l >> 4) & 3).
@@ -250,20 +250,6 @@ __global__ void __launch_bounds__(256) conv_splitk_finish_kernel(SpxArgs a) {
     cdf_epilogue_rows<BN, BM, 256>(a, a.ph[0], a.y, cs, tile_m * BM, tile_n * BN, M, tid, [](int p) { return p; });
 }
 
-static int fill_phases(SpPhase* ph, int nphase, const int* pd, const char* who) {
-    for (int p = 0; p < nphase; ++p) {
-        ph[p].oy = pd[0]; ph[p].ox = pd[1]; ph[p].ntaps = pd[2];
-        CDF_REQUIRE(pd[2] >= 0 && pd[2] <= CDF_MAX_TAPS, "%s: too many taps (%d)", who, pd[2]);
-        for (int t = 0; t < pd[2]; ++t) {
-            ph[p].dy[t] = (signed char)pd[3 + 3 * t];
-            ph[p].dx[t] = (signed char)pd[4 + 3 * t];
-            ph[p].wi[t] = (signed char)pd[5 + 3 * t];
-        }
-        pd += 3 + 3 * pd[2];
-    }
-    return CDF_OK;
-}
-
 extern "C" int cdf_gemm_tuning_default(cdf_gemm_tuning* t) {
     CDF_REQUIRE(t, "cdf_gemm_tuning_default: null pointer");
     *t = kTuneDefault;
@@ -299,8 +285,8 @@ static int spx_ksplit(int M, int Cout, int nphase, int ntaps, const cdf_gemm_tun
 extern "C" int cdf_conv_gemm_bf16x_ksplit(int M, int Cout, int nphase, int ntaps, const cdf_gemm_tuning* tune) { return spx_ksplit(M, Cout, nphase, ntaps, *cdf_tune(tune)); }
 
 template <int NS>
-static int dispatch_gemm_bf16x(SpxArgs& a, int B, int H, int W, int Cin, int Cout, int QH, int QW, int os, int is, int nphase, long long ks_ws_floats,
-                               const cdf_gemm_tuning& T, hipStream_t s, int* bm_out = nullptr, CdfPlan* plan = nullptr) {
+static int dispatch_gemm_bf16x(SpxArgs& a, long long ks_ws_floats, const cdf_gemm_tuning& T, hipStream_t s, int* bm_out = nullptr, CdfPlan* plan = nullptr) {
+    const int B = a.B, H = a.H, W = a.W, Cin = a.Cin, Cout = a.Cout, QH = a.QH, QW = a.QW, os = a.os, is = a.is, nphase = a.nphase;
     // Tile choice: 64-wide N for Cout <= 64 (no half-empty MFMA columns); 64-row M tiles when 128-row tiles would
     // leave most of the 256 CUs x 2 resident blocks idle (deep, small-image layers: M = 8192 at 16 x 16); the 8-wave
     // 256 x 128 tile (3 stages, one block per CU) when it still gives every CU at least ~2 tiles.
@@ -428,23 +414,18 @@ extern "C" int cdf_conv_gemm_bf16x_io(const void* x_hi, const void* x_lo, int ld
     CDF_REQUIRE(!mul_mode || mul, "cdf_conv_gemm_bf16x: mul_mode without mul tensor");
     SpxArgs a;
     a.x_hi = (const unsigned short*)x_hi; a.x_lo = (const unsigned short*)x_lo; a.zero = (const unsigned short*)zero;
-    a.w_hi = (const unsigned short*)w_hi; a.w_lo = (const unsigned short*)w_lo; a.y = y;
-    a.bias = bias; a.sbias = sbias; a.res = res; a.pre = pre; a.mul = mul;
-    a.ldx = ldx; a.ldk = ldk; a.ldy = ldy; a.ld_sbias = ld_sbias; a.ldr = ldr; a.ldp = ldp; a.ldm = ldm;
-    a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.OH = OH; a.OW = OW; a.Cout = Cout; a.QH = QH; a.QW = QW; a.os = os; a.is = is;
-    a.act = act; a.mul_mode = mul_mode; a.accumulate = accumulate; a.nphase = nphase;
-    a.vec = cdf_epi_vec_ok(Cout, y, ldy, bias, sbias, ld_sbias, res, ldr, pre, ldp, mul, ldm);
-    a.ys_hi = (unsigned short*)y_hi; a.ys_lo = (unsigned short*)y_lo; a.ld_ys = ld_ys;
-    a.io_bf = io_bf16;
-    a.epi = cdf_tune(tune)->epilogue ? cdf_epi_select(a) : 0;
-    a.ln_x = nullptr; a.ln_mean = nullptr; a.ln_rstd = nullptr; a.ln_part = nullptr; a.ld_lnx = 0;
+    a.w_hi = (const unsigned short*)w_hi; a.w_lo = (const unsigned short*)w_lo; a.ldx = ldx; a.ldk = ldk;
+    cdf_fill_gemm_common(a, y, ldy, bias, sbias, ld_sbias, res, ldr, pre, ldp, mul, ldm, B, H, W, Cin, OH, OW, Cout, QH, QW, os, is, nphase, act, mul_mode,
+                         accumulate, y_hi, y_lo, ld_ys, io_bf16);
+    cdf_clear_epi(a);
+    if (cdf_tune(tune)->epilogue) a.epi = cdf_epi_select(a);
     CDF_REQUIRE(!y_hi || a.vec, "cdf_conv_gemm_bf16x: split output planes need the vectorised epilogue (aligned pointers, pitches %% 4)");
     CDF_REQUIRE(!(io_bf16 & 7) || a.vec, "cdf_conv_gemm_bf16x_io: bf16 epilogue operands need the vectorised epilogue (16-byte-aligned pointers, pitches %% 4, Cout %% 4)");
-    int rc = fill_phases(a.ph, nphase, phase_desc, "cdf_conv_gemm_bf16x");
+    int rc = cdf_fill_phases(a.ph, nphase, phase_desc, "cdf_conv_gemm_bf16x");
     if (rc) return rc;
     a.ksplit = 1; a.ks_ws = ws; a.ks_ld = 0;
-    return x_lo ? dispatch_gemm_bf16x<3>(a, B, H, W, Cin, Cout, QH, QW, os, is, nphase, ws ? ws_floats : 0, *cdf_tune(tune), CDF_S)
-                : dispatch_gemm_bf16x<1>(a, B, H, W, Cin, Cout, QH, QW, os, is, nphase, ws ? ws_floats : 0, *cdf_tune(tune), CDF_S);
+    return x_lo ? dispatch_gemm_bf16x<3>(a, ws ? ws_floats : 0, *cdf_tune(tune), CDF_S)
+                : dispatch_gemm_bf16x<1>(a, ws ? ws_floats : 0, *cdf_tune(tune), CDF_S);
 }
 
 
@@ -472,15 +453,15 @@ extern "C" int cdf_conv_gemm_bf16x_form(int B, int H, int W, int Cin, int Cout, 
     CDF_TUNE_CHECK(tune, "cdf_conv_gemm_bf16x_form");
     CDF_REQUIRE(!lnbwd || cdf_conv_gemm_bf16x_lnbwd_ok(B, H, W, Cin, Cout, nphase, phase_desc[2]), "cdf_conv_gemm_bf16x_form: not a geometry of cdf_conv_gemm_bf16x_lnbwd");
     SpxArgs a = {};
-    a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.QH = QH; a.QW = QW; a.os = os; a.is = is; a.nphase = nphase;
-    int rc = fill_phases(a.ph, nphase, phase_desc, "cdf_conv_gemm_bf16x_form");
+    cdf_fill_gemm_common(a, nullptr, 0, nullptr, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 0, B, H, W, Cin, 0, 0, Cout, QH, QW, os, is, nphase, 0, 0, 0, nullptr, nullptr, 0, 0);
+    int rc = cdf_fill_phases(a.ph, nphase, phase_desc, "cdf_conv_gemm_bf16x_form");
     if (rc) return rc;
     static float ws_token;                                   // (the dispatcher only asks whether a workspace was given; nothing is launched)
     a.ksplit = 1; a.ks_ws = (ws_floats > 0 && !lnbwd) ? &ws_token : nullptr; a.ks_ld = 0;
     const cdf_gemm_tuning T = lnbwd ? lnbwd_tuning(tune) : *cdf_tune(tune);
     CdfPlan plan = {0, 0, 0};
-    rc = ns == 3 ? dispatch_gemm_bf16x<3>(a, B, H, W, Cin, Cout, QH, QW, os, is, nphase, a.ks_ws ? ws_floats : 0, T, nullptr, nullptr, &plan)
-                 : dispatch_gemm_bf16x<1>(a, B, H, W, Cin, Cout, QH, QW, os, is, nphase, a.ks_ws ? ws_floats : 0, T, nullptr, nullptr, &plan);
+    rc = ns == 3 ? dispatch_gemm_bf16x<3>(a, a.ks_ws ? ws_floats : 0, T, nullptr, nullptr, &plan)
+                 : dispatch_gemm_bf16x<1>(a, a.ks_ws ? ws_floats : 0, T, nullptr, nullptr, &plan);
     if (rc) return rc;
     if (tiles_grid) { tiles_grid[0] = plan.tiles; tiles_grid[1] = plan.grid; }
     return plan.code;
@@ -499,20 +480,18 @@ extern "C" int cdf_conv_gemm_bf16x_lnbwd(const void* x_hi, const void* x_lo, int
                 "cdf_conv_gemm_bf16x_lnbwd: alignment / pitches");
     SpxArgs a;
     a.x_hi = (const unsigned short*)x_hi; a.x_lo = (const unsigned short*)x_lo; a.zero = (const unsigned short*)zero;
-    a.w_hi = (const unsigned short*)w_hi; a.w_lo = (const unsigned short*)w_lo; a.y = dh;
-    a.bias = ln_g; a.sbias = nullptr; a.res = nullptr; a.pre = nullptr; a.mul = nullptr;
-    a.ldx = ldx; a.ldk = ldk; a.ldy = lddh; a.ld_sbias = 0; a.ldr = 0; a.ldp = 0; a.ldm = 0;
-    a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.OH = H; a.OW = W; a.Cout = Cout; a.QH = H; a.QW = W; a.os = 1; a.is = 1;
-    a.act = 0; a.mul_mode = 0; a.accumulate = 0; a.nphase = 1; a.vec = 1;
-    a.ys_hi = nullptr; a.ys_lo = nullptr; a.ld_ys = 0; a.io_bf = 0;
+    a.w_hi = (const unsigned short*)w_hi; a.w_lo = (const unsigned short*)w_lo; a.ldx = ldx; a.ldk = ldk;
+    // y = dh, "bias" = the LayerNorm's gain, one 3 x 3 stride-1 phase, no other operand
+    cdf_fill_gemm_common(a, dh, lddh, ln_g, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 0, B, H, W, Cin, H, W, Cout, H, W, 1, 1, 1, 0, 0, 0, nullptr, nullptr, 0, 0);
+    a.vec = 1;                                               // (what the checks above guarantee)
     a.epi = CDF_EPI_LNBWD;
     a.ln_x = ln_x; a.ln_mean = ln_mean; a.ln_rstd = ln_rstd; a.ln_part = part; a.ld_lnx = ld_lnx;
-    int rc = fill_phases(a.ph, 1, phase_desc, "cdf_conv_gemm_bf16x_lnbwd");
+    int rc = cdf_fill_phases(a.ph, 1, phase_desc, "cdf_conv_gemm_bf16x_lnbwd");
     if (rc) return rc;
     a.ksplit = 1; a.ks_ws = nullptr; a.ks_ld = 0;
     const cdf_gemm_tuning T = lnbwd_tuning(tune);
     int bm = 0;
-    rc = x_lo ? dispatch_gemm_bf16x<3>(a, B, H, W, Cin, Cout, H, W, 1, 1, 1, 0, T, CDF_S, &bm) : dispatch_gemm_bf16x<1>(a, B, H, W, Cin, Cout, H, W, 1, 1, 1, 0, T, CDF_S, &bm);
+    rc = x_lo ? dispatch_gemm_bf16x<3>(a, 0, T, CDF_S, &bm) : dispatch_gemm_bf16x<1>(a, 0, T, CDF_S, &bm);
     if (rc) return rc;
     CDF_REQUIRE(bm == 64 || bm == 128 || bm == 256, "cdf_conv_gemm_bf16x_lnbwd: the dispatcher reported no row tile");
     return cdf_norm_param_reduce(part, (int)((long long)B * H * W / bm), Cout, dg, db, 1, stream);

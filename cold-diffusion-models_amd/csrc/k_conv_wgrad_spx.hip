@@ -542,26 +542,16 @@ static int dispatch_wgrad_bf16x(SpxWgradArgs& a, int QH, int QW, int HA, int WA,
     return launch_wgrad_spx<NS, 128, 128>(a, s, plan);
 }
 
-static void fill_wgrad_taps(SpxWgradArgs& a, int ntaps, const int* tap_desc) {
-    for (int t = 0; t < ntaps; ++t) {
-        a.day[t] = (signed char)tap_desc[4 * t + 0];
-        a.dax[t] = (signed char)tap_desc[4 * t + 1];
-        a.dby[t] = (signed char)tap_desc[4 * t + 2];
-        a.dbx[t] = (signed char)tap_desc[4 * t + 3];
-    }
-}
-
 // The kernel a cdf_conv_wgrad_bf16x call of this geometry launches: dispatch_wgrad_bf16x itself, stopped before the launch.
 extern "C" int cdf_conv_wgrad_bf16x_form(int QH, int QW, int HA, int WA, int sa, int HB, int WB, int sb, int CA, int CB, int ntaps, const int* tap_desc,
                                          int ns, int nsplit, const cdf_gemm_tuning* tune, int* tiles_grid) {
-    CDF_REQUIRE(ntaps >= 1 && ntaps <= CDF_MAX_TAPS && tap_desc && nsplit >= 1 && (ns == 1 || ns == 3), "cdf_conv_wgrad_bf16x_form: bad arguments");
+    CDF_REQUIRE(ns == 1 || ns == 3, "cdf_conv_wgrad_bf16x_form: bad arguments");
     CDF_TUNE_CHECK(tune, "cdf_conv_wgrad_bf16x_form");
     SpxWgradArgs a = {};
-    a.QH = QH; a.QW = QW; a.HA = HA; a.WA = WA; a.sa = sa; a.HB = HB; a.WB = WB; a.sb = sb;
-    a.CA = CA; a.CB = CB; a.ntaps = ntaps; a.nsplit = nsplit;
-    fill_wgrad_taps(a, ntaps, tap_desc);
+    int rc = cdf_fill_wgrad_geom(a, "cdf_conv_wgrad_bf16x_form", 0, QH, QW, HA, WA, sa, HB, WB, sb, CA, CB, ntaps, tap_desc, nsplit, 32);   // (no batch: nothing is launched)
+    if (rc) return rc;
     CdfPlan plan = {0, 0, 0};
-    const int rc = ns == 3 ? dispatch_wgrad_bf16x<3>(a, QH, QW, HA, WA, sa, HB, WB, sb, CA, CB, ntaps, *cdf_tune(tune), nullptr, &plan)
+    rc = ns == 3 ? dispatch_wgrad_bf16x<3>(a, QH, QW, HA, WA, sa, HB, WB, sb, CA, CB, ntaps, *cdf_tune(tune), nullptr, &plan)
                            : dispatch_wgrad_bf16x<1>(a, QH, QW, HA, WA, sa, HB, WB, sb, CA, CB, ntaps, *cdf_tune(tune), nullptr, &plan);
     if (rc) return rc;
     if (tiles_grid) { tiles_grid[0] = plan.tiles; tiles_grid[1] = plan.grid; }
@@ -577,16 +567,12 @@ extern "C" int cdf_conv_wgrad_bf16x(const void* a_hi, const void* a_lo, int lda,
     CDF_REQUIRE((a_lo != nullptr) == (b_lo != nullptr), "cdf_conv_wgrad_bf16x: pass both lo planes (split precision) or neither (single-pass bf16)");
     CDF_REQUIRE(((((uintptr_t)a_hi) | ((uintptr_t)a_lo) | ((uintptr_t)b_hi) | ((uintptr_t)b_lo) | ((uintptr_t)zero)) & 15) == 0, "cdf_conv_wgrad_bf16x: operands must be 16B aligned");
     CDF_REQUIRE(lda % 8 == 0 && ldb % 8 == 0 && CA % 8 == 0 && CB % 8 == 0 && lda >= CA && ldb >= CB && ldo % 4 == 0 && ldo >= CB, "cdf_conv_wgrad_bf16x: channels / pitches must be multiples of 8");
-    CDF_REQUIRE(ntaps >= 1 && ntaps <= CDF_MAX_TAPS && tap_desc && nsplit >= 1, "cdf_conv_wgrad_bf16x: bad tap / split count");
     SpxWgradArgs a;
+    const int rc = cdf_fill_wgrad_geom(a, "cdf_conv_wgrad_bf16x", B, QH, QW, HA, WA, sa, HB, WB, sb, CA, CB, ntaps, tap_desc, nsplit, 32);
+    if (rc) return rc;
     a.a_hi = (const unsigned short*)a_hi; a.a_lo = (const unsigned short*)a_lo; a.b_hi = (const unsigned short*)b_hi;
     a.b_lo = (const unsigned short*)b_lo; a.zero = (const unsigned short*)zero; a.out = ws; a.bsum = bsum;
-    a.lda = lda; a.ldb = ldb; a.ldo = ldo;
-    a.B = B; a.QH = QH; a.QW = QW; a.HA = HA; a.WA = WA; a.sa = sa; a.HB = HB; a.WB = WB; a.sb = sb;
-    a.CA = CA; a.CB = CB; a.ntaps = ntaps; a.nsplit = nsplit; a.xcd_swizzle = cdf_tune(tune)->wgrad_swizzle;
-    const int M = B * QH * QW;
-    a.m_per_split = cdf_cdiv(cdf_cdiv(M, nsplit), 32) * 32;
-    fill_wgrad_taps(a, ntaps, tap_desc);
+    a.lda = lda; a.ldb = ldb; a.ldo = ldo; a.xcd_swizzle = cdf_tune(tune)->wgrad_swizzle;
     return a_lo ? dispatch_wgrad_bf16x<3>(a, QH, QW, HA, WA, sa, HB, WB, sb, CA, CB, ntaps, *cdf_tune(tune), CDF_S)
                 : dispatch_wgrad_bf16x<1>(a, QH, QW, HA, WA, sa, HB, WB, sb, CA, CB, ntaps, *cdf_tune(tune), CDF_S);
 }
