@@ -228,7 +228,8 @@ COVERED_AT_PRODUCTION_SHAPE = {
     "cdf_conv_gemm_bf16x_io": [_GP + "test_gemm_bench_forms", _K + "test_conv_presplit_large", _P2 + "test_bf16_mode_bench_shape_fused_step"],
     # elementwise bf16 -> fp32 widening (exactness: test_bf16_storage.py::test_bf16_to_f32_and_back)
     "cdf_bf16_to_f32": [_P2 + "test_bf16_mode_bench_shape_fused_step", "test_bf16_storage.py::test_bf16_to_f32_and_back"],
-    # GEMM-class entry points in the plain bf16 arithmetic
+    # the in-kernel-split GEMM pair (csrc/k_conv_sp.hip): the 1 x 1 projections and their gradients in BOTH arithmetic modes -- split = 3
+    # under bf16x3, split = 1 under bf16 (form by form: test_gemm_sp_forms.py, appended below)
     "cdf_conv_gemm_bf16": [_K + "test_conv_gemm_bf16_large"],
     "cdf_conv_wgrad_bf16": [_K + "test_conv_gemm_bf16_large"],
     # elementwise and layout operations: the bench-shape step.  (They have no reduction or tile walk, but they are not free of a clamp that
@@ -251,6 +252,11 @@ _FF = "test_gemm_f32_forms.py::"
 COVERED_AT_PRODUCTION_SHAPE["cdf_conv_gemm"] += [_FF + "test_igemm_single_launch", _FF + "test_igemm_batched_call_sites"]
 COVERED_AT_PRODUCTION_SHAPE["cdf_conv_gemm_io"] += [_FF + "test_igemm_single_launch", _FF + "test_igemm_batched_call_sites"]
 COVERED_AT_PRODUCTION_SHAPE["cdf_conv_wgrad"] += [_FF + "test_wgrad_tiles_plans_splits", _FF + "test_wgrad_batched_and_head_split"]
+# the in-kernel-split pair: every geometry, tile edge, epilogue path, layout and slab walk the product launches (test_coverage_guard holds
+# the recordings against that module's form tables)
+_SF = "test_gemm_sp_forms.py::"
+COVERED_AT_PRODUCTION_SHAPE["cdf_conv_gemm_bf16"] += [_SF + "test_sp_gemm_forms"]
+COVERED_AT_PRODUCTION_SHAPE["cdf_conv_wgrad_bf16"] += [_SF + "test_sp_wgrad_plans_and_splits"]
 # entry points with nothing shape-dependent to test at scale, with the reason
 EXEMPT = {
     "cdf_last_error": "host-side error string",
@@ -266,15 +272,16 @@ EXEMPT = {
 }
 
 
-_GEMM_FAMILY = ("cdf_conv_gemm_bf16x", "cdf_conv_gemm_bf16x_io", "cdf_conv_gemm_bf16x_lnbwd", "cdf_conv_wgrad_bf16x", "cdf_conv_wgrad")
+_SP_GEMM = ("cdf_conv_gemm_bf16", "cdf_conv_wgrad_bf16")     # the in-kernel-split pair: guarded form by form too (test_gemm_sp_forms.py)
+_GEMM_FAMILY = ("cdf_conv_gemm_bf16x", "cdf_conv_gemm_bf16x_io", "cdf_conv_gemm_bf16x_lnbwd", "cdf_conv_wgrad_bf16x", "cdf_conv_wgrad") + _SP_GEMM
 _F32_GEMM = ("cdf_conv_gemm", "cdf_conv_gemm_io")            # the exact-fp32 pair: guarded form by form too (test_gemm_f32_forms.py)
 
 
 def _guard_calls(bench_data):
     """Every cdf_* call of one bench step in each arithmetic mode the bench reports (bf16x3, and bf16 with its bf16 activation
     stream) and of one sampler step: (set of names, the (nsplit, T, R, C) of the bf16x3 step's slab reductions, the (recording, name,
-    arguments) of every pre-split GEMM / weight-gradient call of those and of one forward + backward pass of config 2's network -- the
-    phase / tap descriptors copied, they are buffers the caller may reuse)."""
+    arguments) of every GEMM / weight-gradient call (pre-split family, exact-fp32 pair, in-kernel-split pair) of those and of one
+    forward + backward pass of config 2's network -- the phase / tap descriptors copied, they are buffers the caller may reuse)."""
     from colddiff import runtime as rt
     names, unpack, gemm = set(), set(), []
 
@@ -330,7 +337,8 @@ def test_coverage_guard(bench_data):
     cdf_conv_wgrad_bf16x_form) with the recorded arguments -- must be a form some test_gemm_production.BENCH_GEMM / BENCH_WGRAD row resolves
     to, and every committed row must still be a call the recordings contain.  The exact-fp32 pair (cdf_conv_gemm, cdf_conv_gemm_io,
     cdf_conv_wgrad) likewise: every form (test_gemm_f32_forms.f32_gemm_form / f32_wgrad_form of the recorded arguments) must be one a row
-    of that module's case tables has, and the forms it flags as reached must still be reached."""
+    of that module's case tables has, and the forms it flags as reached must still be reached.  The in-kernel-split pair
+    (cdf_conv_gemm_bf16, cdf_conv_wgrad_bf16) the same way against test_gemm_sp_forms (sp_gemm_form / sp_wgrad_form)."""
     import os
     import re
     from test_kernels_production import BENCH_UNPACK
@@ -354,7 +362,7 @@ def test_coverage_guard(bench_data):
         if name == "cdf_conv_wgrad_bf16x":
             reached_w.setdefault((_wgrad_code(L, name, a), 3 if a[1] else 1), (src, a[9:21], a[22]))
             rows_w.add(gp.wgrad_row(name, a))
-        elif name != "cdf_conv_wgrad" and name not in _F32_GEMM:
+        elif name != "cdf_conv_wgrad" and name not in _F32_GEMM and name not in _SP_GEMM:
             reached_g.setdefault((_gemm_code(L, name, a), 3 if a[1] else 1), (src, name, a[9:21]))
             rows_g.add(gp.gemm_row(name, a))
     assert all(c > 0 for c, _ in list(reached_g) + list(reached_w)), (reached_g, reached_w)
@@ -388,3 +396,21 @@ def test_coverage_guard(bench_data):
         assert not untested, "exact-fp32 %s forms the product reaches without a test_gemm_f32_forms row: %s" % (what, untested)
         stale = sorted(flagged - set(reached), key=repr)
         assert not stale, "test_gemm_f32_forms flags %s forms as reached that the recordings no longer contain: %s" % (what, stale)
+    # ---- the in-kernel-split pair (conv_igemm_sp_kernel, conv_wgrad_sp_kernel), form by form
+    import test_gemm_sp_forms as sf
+    reached_sg, reached_sw = {}, {}
+    for src, name, a in gemm:
+        if name == "cdf_conv_gemm_bf16":
+            reached_sg.setdefault(sf.sp_gemm_form(a), (src, a[1], a[6:19], a[24]))
+        elif name == "cdf_conv_wgrad_bf16":
+            reached_sw.setdefault(sf.sp_wgrad_form(a), (src, a[1], a[3], a[6:18], a[19]))
+    assert reached_sg and reached_sw
+    for what, reached, tested, flagged in (("GEMM", reached_sg, sf.forms_of_gemm_rows(), sf.REACHED_SP_GEMM),
+                                           ("weight-gradient", reached_sw, sf.forms_of_wgrad_rows(), sf.REACHED_SP_WGRAD)):
+        print("in-kernel-split %s forms reached:" % what)
+        for k in sorted(reached, key=repr):
+            print("    %r," % (k,))
+        untested = {k: v for k, v in reached.items() if k not in tested}
+        assert not untested, "in-kernel-split %s forms the product reaches without a test_gemm_sp_forms row: %s" % (what, untested)
+        stale = sorted(flagged - set(reached), key=repr)
+        assert not stale, "test_gemm_sp_forms flags %s forms as reached that the recordings no longer contain: %s" % (what, stale)
