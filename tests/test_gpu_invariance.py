@@ -257,6 +257,17 @@ COVERED_AT_PRODUCTION_SHAPE["cdf_conv_wgrad"] += [_FF + "test_wgrad_tiles_plans_
 _SF = "test_gemm_sp_forms.py::"
 COVERED_AT_PRODUCTION_SHAPE["cdf_conv_gemm_bf16"] += [_SF + "test_sp_gemm_forms"]
 COVERED_AT_PRODUCTION_SHAPE["cdf_conv_wgrad_bf16"] += [_SF + "test_sp_wgrad_plans_and_splits"]
+# the depthwise, LayerNorm and GroupNorm entry points: every pitch, null-pointer, accumulate and tile / chunk form the product launches
+# (test_coverage_guard holds the recordings against that module's form tables)
+_ND = "test_norm_dw_forms.py::"
+for _names, _test in ((("cdf_dwconv7", "cdf_dwconv7_io", "cdf_dwconv7_planes"), "test_dwconv7_forms"),
+                      (("cdf_dwconv7_wgrad", "cdf_dwconv7_wgrad_io", "cdf_dwconv7_wgrad_nchunk"), "test_dwconv7_wgrad_forms"),
+                      (("cdf_layernorm_c_fwd", "cdf_layernorm_c_fwd_io", "cdf_layernorm_blocks"), "test_layernorm_fwd_forms"),
+                      (("cdf_layernorm_c_bwd", "cdf_layernorm_c_bwd_io", "cdf_layernorm_c_bwd_planes", "cdf_layernorm_blocks"), "test_layernorm_bwd_forms"),
+                      (("cdf_groupnorm_fwd_ex", "cdf_groupnorm_nchunk"), "test_groupnorm_fwd_forms"),
+                      (("cdf_groupnorm_bwd_ex", "cdf_groupnorm_nchunk"), "test_groupnorm_bwd_forms")):
+    for _name in _names:
+        COVERED_AT_PRODUCTION_SHAPE[_name].append(_ND + _test)
 # entry points with nothing shape-dependent to test at scale, with the reason
 EXEMPT = {
     "cdf_last_error": "host-side error string",
@@ -275,13 +286,20 @@ EXEMPT = {
 _SP_GEMM = ("cdf_conv_gemm_bf16", "cdf_conv_wgrad_bf16")     # the in-kernel-split pair: guarded form by form too (test_gemm_sp_forms.py)
 _GEMM_FAMILY = ("cdf_conv_gemm_bf16x", "cdf_conv_gemm_bf16x_io", "cdf_conv_gemm_bf16x_lnbwd", "cdf_conv_wgrad_bf16x", "cdf_conv_wgrad") + _SP_GEMM
 _F32_GEMM = ("cdf_conv_gemm", "cdf_conv_gemm_io")            # the exact-fp32 pair: guarded form by form too (test_gemm_f32_forms.py)
+# the kernels between the GEMMs (csrc/k_dwconv.hip, csrc/k_norm.hip): guarded form by form too (test_norm_dw_forms.py); their calls are
+# kept with the GEMM calls
+_NORM_DW = ("cdf_dwconv7", "cdf_dwconv7_io", "cdf_dwconv7_planes", "cdf_dwconv7_wgrad", "cdf_dwconv7_wgrad_io", "cdf_layernorm_c_fwd",
+            "cdf_layernorm_c_fwd_io", "cdf_layernorm_c_bwd", "cdf_layernorm_c_bwd_io", "cdf_layernorm_c_bwd_planes", "cdf_groupnorm_fwd",
+            "cdf_groupnorm_fwd_ex", "cdf_groupnorm_bwd", "cdf_groupnorm_bwd_ex")
+_GEMM_FAMILY += _NORM_DW
 
 
 def _guard_calls(bench_data):
     """Every cdf_* call of one bench step in each arithmetic mode the bench reports (bf16x3, and bf16 with its bf16 activation
     stream) and of one sampler step: (set of names, the (nsplit, T, R, C) of the bf16x3 step's slab reductions, the (recording, name,
-    arguments) of every GEMM / weight-gradient call (pre-split family, exact-fp32 pair, in-kernel-split pair) of those and of one
-    forward + backward pass of config 2's network -- the phase / tap descriptors copied, they are buffers the caller may reuse)."""
+    arguments) of every GEMM / weight-gradient call (pre-split family, exact-fp32 pair, in-kernel-split pair) and of every depthwise,
+    LayerNorm and GroupNorm call (_NORM_DW) of those and of one forward + backward pass of config 2's network (dropout 0.1, training mode)
+    -- the phase / tap descriptors copied, they are buffers the caller may reuse)."""
     from colddiff import runtime as rt
     names, unpack, gemm = set(), set(), []
 
@@ -338,7 +356,8 @@ def test_coverage_guard(bench_data):
     to, and every committed row must still be a call the recordings contain.  The exact-fp32 pair (cdf_conv_gemm, cdf_conv_gemm_io,
     cdf_conv_wgrad) likewise: every form (test_gemm_f32_forms.f32_gemm_form / f32_wgrad_form of the recorded arguments) must be one a row
     of that module's case tables has, and the forms it flags as reached must still be reached.  The in-kernel-split pair
-    (cdf_conv_gemm_bf16, cdf_conv_wgrad_bf16) the same way against test_gemm_sp_forms (sp_gemm_form / sp_wgrad_form)."""
+    (cdf_conv_gemm_bf16, cdf_conv_wgrad_bf16) the same way against test_gemm_sp_forms (sp_gemm_form / sp_wgrad_form).  The depthwise,
+    LayerNorm and GroupNorm entry points (_NORM_DW) the same way against the six classifiers and case tables of test_norm_dw_forms."""
     import os
     import re
     from test_kernels_production import BENCH_UNPACK
@@ -362,7 +381,7 @@ def test_coverage_guard(bench_data):
         if name == "cdf_conv_wgrad_bf16x":
             reached_w.setdefault((_wgrad_code(L, name, a), 3 if a[1] else 1), (src, a[9:21], a[22]))
             rows_w.add(gp.wgrad_row(name, a))
-        elif name != "cdf_conv_wgrad" and name not in _F32_GEMM and name not in _SP_GEMM:
+        elif name != "cdf_conv_wgrad" and name not in _F32_GEMM and name not in _SP_GEMM and name not in _NORM_DW:
             reached_g.setdefault((_gemm_code(L, name, a), 3 if a[1] else 1), (src, name, a[9:21]))
             rows_g.add(gp.gemm_row(name, a))
     assert all(c > 0 for c, _ in list(reached_g) + list(reached_w)), (reached_g, reached_w)
@@ -414,3 +433,17 @@ def test_coverage_guard(bench_data):
         assert not untested, "in-kernel-split %s forms the product reaches without a test_gemm_sp_forms row: %s" % (what, untested)
         stale = sorted(flagged - set(reached), key=repr)
         assert not stale, "test_gemm_sp_forms flags %s forms as reached that the recordings no longer contain: %s" % (what, stale)
+    # ---- the kernels between the GEMMs (k_dwconv.hip, k_norm.hip), form by form
+    import test_norm_dw_forms as nd
+    assert set(nd.ALL_NAMES) == set(_NORM_DW)
+    reached_nd = nd.reached_forms(gemm)
+    for what, reached in reached_nd.items():
+        tested, flagged = nd.forms_of_rows(what), nd.REACHED[what]
+        print("%s forms reached:" % what)
+        for k in sorted(reached, key=repr):
+            print("    %r," % (k,))
+        assert reached, what
+        untested = {k: v for k, v in reached.items() if k not in tested}
+        assert not untested, "%s forms the product reaches without a test_norm_dw_forms row: %s" % (what, untested)
+        stale = sorted(flagged - set(reached), key=repr)
+        assert not stale, "test_norm_dw_forms flags %s forms as reached that the recordings no longer contain: %s" % (what, stale)
