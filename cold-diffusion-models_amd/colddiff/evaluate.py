@@ -4,7 +4,8 @@ Mirrors deblurring_diffusion_pytorch.py:1238-1267 (test_from_data), 1391-1456 (s
 1459-1511 (sample_as_a_mean_blur_torch_gmm), 1514-1564 (sample_as_a_blur_torch_gmm), 1567-1702
 (fid_distance_decrease_from_manifold) and 1712-1722 (save_training_data): same method names, arguments, file names.  What they
 call on the diffusion model (all_sample / gen_sample / gen_sample_2 / opt / sample_from_blur) runs on the HIP kernels; the
-Gaussian-mixture fit is CPU work upstream too (pycave there, scikit-learn's GaussianMixture here behind the same small API).
+Gaussian-mixture fit of `torch_gmm=None` is scikit-learn's GaussianMixture on the host behind pycave's small API (`GMM` below);
+`colddiff.gmm.GaussianMixture` is the class to pass as `torch_gmm` for a fit on the device, as upstream's drivers do with pycave.
 Image titles / cv2 montages (add_title, the paper_* figure methods) are figure code and stay out of scope.
 """
 import os
@@ -265,7 +266,8 @@ class GenEvalMixin:
     except `sample_and_save_for_fid`): denoising_diffusion_pytorch.py:821-854, 1091-1395; demixing_diffusion_pytorch.py:806-836,
     1080-1384; defading-generation .../defading_diffusion_pytorch.py:868-904, 1148-1452.  Same names, arguments, folders and file names;
     the samplers they drive (`gen_sample`, `all_sample`) run on the HIP kernels, the Gaussian-mixture fit is scikit-learn on the host as
-    upstream (`GaussianMixture(n_components, random_state=0)`), pycave's `torch_gmm` goes through `EvalMixin._fit_gmm`.  Upstream calls
+    upstream (`GaussianMixture(n_components, random_state=0)`) unless the trailing `device_gmm=True` asks for `colddiff.gmm`, pycave's
+    `torch_gmm` goes through `EvalMixin._fit_gmm` (`colddiff.gmm.GaussianMixture` is a device-side class to pass there).  Upstream calls
     `self.ema_model.all_sample` without `.module` (an AttributeError under DataParallel): here `ema_core`.  The hard-coded sample counts
     (6400 / 10000 / 100 per round, batches of 128 / 1000) are the defaults of trailing keyword arguments; titles and GIFs are figure code."""
 
@@ -318,7 +320,13 @@ class GenEvalMixin:
                 break
         return torch.stack(rows)
 
-    def _sk_gmm(self, feats, clusters):
+    def _sk_gmm(self, feats, clusters, device_gmm=False):
+        """scikit-learn's mixture on the host as upstream; device_gmm: `colddiff.gmm.GaussianMixture` with scikit-learn's defaults (tol 1e-3,
+        reg_covar 1e-6, random_state 0) on the device the features are on, behind scikit-learn's `.sample(n) -> (X, labels)`."""
+        if device_gmm:
+            from . import gmm
+            model = gmm.GaussianMixture(num_components=clusters, convergence_tolerance=1e-3, covariance_regularization=1e-6, random_state=0)
+            return gmm.SklearnStyle(model.fit(feats.detach().float().to(self.device)))
         from sklearn.mixture import GaussianMixture
         return GaussianMixture(n_components=clusters, random_state=0).fit(feats.detach().float().cpu().numpy())
 
@@ -327,8 +335,8 @@ class GenEvalMixin:
         og_x = torch.as_tensor(og_x).reshape(n, ch, siz, siz).to(self.device).float()
         return F.interpolate(og_x, size=self.image_size, mode='bilinear').contiguous()
 
-    def sample_as_a_vector_gmm(self, start=0, end=1000, siz=64, ch=3, clusters=10, num_samples=100):
-        gm = self._sk_gmm(self._dataset_vectors(start, end, siz), clusters)
+    def sample_as_a_vector_gmm(self, start=0, end=1000, siz=64, ch=3, clusters=10, num_samples=100, device_gmm=False):
+        gm = self._sk_gmm(self._dataset_vectors(start, end, siz), clusters, device_gmm)
         og_x, _ = gm.sample(n_samples=num_samples)
         og_img = self._up(og_x, num_samples, ch, siz)
         X_0s, X_ts = self._all_sample(1, og_img)
@@ -340,8 +348,9 @@ class GenEvalMixin:
                 self._save(X_ts[i], str(self.results_folder / f'sample-{start}-{end}-{siz}-{clusters}-{i}-{extra_path}-xt.png'))
         return X_0s, X_ts
 
-    def sample_as_a_vector_gmm_and_save(self, start=0, end=1000, siz=64, ch=3, clusters=10, n_sample=10000, num_samples=10000):
-        gm = self._sk_gmm(self._dataset_vectors(start, end, siz), clusters)
+    def sample_as_a_vector_gmm_and_save(self, start=0, end=1000, siz=64, ch=3, clusters=10, n_sample=10000, num_samples=10000,
+                                        device_gmm=False):
+        gm = self._sk_gmm(self._dataset_vectors(start, end, siz), clusters, device_gmm)
         folder = f'{self.results_folder}_{siz}_{clusters}/'
         _create_folder(folder)
         cnt = 0

@@ -15,38 +15,8 @@
 // tiles, read and written) = 17 MB at d = 2048, ~4 us at HBM speed if it were alone -- not the 2 n d^2 = 0.42 GFLOP of a batch of 50.
 // cdf_gemm_f64 at 2048^3: 17.2 GFLOP; each operand element is read by 32 tiles (2 x 1 GB through L2), C written once (34 MB).
 #include "cdf_common.h"
+#include "cdf_f64_tile.h"     // FID_T / FID_BK / FID_P, fid_chunk_mma, fid_acc_zero: shared with k_gmm.hip
 #include "colddiff.h"
-
-#define FID_T 64     // tile edge
-#define FID_BK 16    // K chunk
-#define FID_P 80     // LDS row pitch in doubles
-
-// The MFMAs of one K chunk: sa / sb are [FID_BK][FID_P], this wave's quarter starts at column 32 wr of sa and 32 wc of sb.
-__device__ __forceinline__ void fid_chunk_mma(const double* sa, const double* sb, f64x4_t (&acc)[2][2], int wr, int wc, int lane) {
-    const int c16 = lane & 15, kq = lane >> 4;
-#pragma unroll
-    for (int ks = 0; ks < FID_BK; ks += 4) {
-        double a[2], b[2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            a[i] = sa[(ks + kq) * FID_P + wr * 32 + i * 16 + c16];
-            b[i] = sb[(ks + kq) * FID_P + wc * 32 + i * 16 + c16];
-        }
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j) acc[i][j] = cdf_mfma_f64_16x16x4(a[i], b[j], acc[i][j]);
-    }
-}
-
-__device__ __forceinline__ void fid_acc_zero(f64x4_t (&acc)[2][2]) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) acc[i][j][r] = 0.0;
-}
 
 // ---- c = alpha a b + diag I --------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) gemm_f64_kernel(const double* A, int lda, const double* B, int ldb, double* C, int ldc, int M, int N,

@@ -28,7 +28,7 @@ extern "C" {
 /* Bumped whenever an exported signature changes incompatibly (rounds 1-3 all answered 1 while arguments were added: `tiled`,
  * `onepass`, `slots`, `tune`).  cdf_abi_version() returns the value the LIBRARY was built with; a binding compares it with the
  * header it was generated from before the first call (colddiff/_lib.py does) -- a mismatched pair would read shifted arguments. */
-#define CDF_ABI_VERSION 12
+#define CDF_ABI_VERSION 13
 
 #define CDF_E_INVALID (-1)
 #define CDF_E_UNSUPPORTED (-2)
@@ -411,6 +411,38 @@ int cdf_moments_merge_f64(double n_b, const double* pivot_b, const double* sum_b
                           const double* pivot_a, double* sum_a, double* outer_a, int ldo_a, int d, void* stream);
 int cdf_gemm_f64(const double* a, int lda, const double* b, int ldb, double* c, int ldc, int m, int n, int k, double alpha, double diag,
                  void* stream);
+
+/* Gaussian mixture on the device (colddiff/gmm.py; the mixture the reference's generation scripts fit with pycave / scikit-learn, e.g.
+ * deblurring_diffusion_pytorch.py:1391-1564): what an EM iteration needs besides cdf_gemm_f64.  All fp64, row-major with row pitches;
+ * a batch is `count` matrices `stride` ELEMENTS apart.  No float atomics, every reduction in a fixed order: two runs are bit-identical.
+ * cdf_potrf_f64: a[k] <- its lower Cholesky factor, in place, blocked right-looking with 64-wide panels (diagonal block in LDS, panel
+ *   solve, trailing update on the f64 matrix-core tile form of cdf_gemm_f64).  Only the lower triangle is read and written; the strict
+ *   upper triangle and the pitch padding are neither.  info[k] (device, `count` ints) = 0, or (index of the first pivot that is not
+ *   positive) + 1: the launch goes on, that matrix's remaining columns are unspecified, the other matrices are not affected.
+ * cdf_trtri_lower_f64: pt[k] = (l[k]^-1)^T, upper triangular; the strict lower triangle of pt[k] is written as zeros (so pt[k] is a plain
+ *   cdf_gemm_f64 operand: the `precisions_cholesky` of scikit-learn).  Only the lower triangle of l is read.  pt must not overlap l.
+ * cdf_tril_copy_f64: out[k] = tril(a[k]) (transpose = 0) or tril(a[k])^T (1), the other triangle zeros; out != a.
+ * cdf_logdet_diag_f64: out[k] = sum_j log m[k][j][j].
+ * cdf_gmm_center_scale_f64: z[i][j] = s_i (x[i][j] - mean[j]), s_i = sqrt(resp[i] / nk[0]) (both read on the device), or s_i = 1 when
+ *   resp and nk are null; x is fp32 (x_is_f64 = 0, widened first) or fp64.  zt, when not null, also receives z^T ([d][n], pitch ldzt).
+ * cdf_rowsumsq_f64: out[i] = sum_j y[i][j]^2, one fixed-order tree per row.
+ * cdf_gmm_resp_f64: maha [K][n] (pitch ldm), logdet [K], logw [K]:
+ *     lp[i][k] = -(d log 2 pi + maha[k][i]) / 2 + logdet[k] + logw[k];   lse_i = logsumexp_k lp[i][k] (shifted by the maximum)
+ *     resp[k][i] = exp(lp[i][k] - lse_i) (pitch ldr);   nk[k] = sum_i resp[k][i] + 10 DBL_EPSILON;   lse_sum[0] = sum_i lse_i
+ *   hard = 1: resp[k][i] = 1 for the k of the largest lp (the lowest index on a tie), 0 elsewhere; lse_sum[0] = 0; logdet / logw may be
+ *   null (zeros) -- the k-means assignment with maha a squared distance.  partial: cdf_gmm_resp_blocks(n) * (K + 1) doubles of scratch. */
+int cdf_potrf_f64(double* a, int lda, long long stride, int d, int count, int* info, void* stream);
+int cdf_trtri_lower_f64(const double* l, int ldl, long long stride_l, double* pt, int ldp, long long stride_p, int d, int count,
+                        void* stream);
+int cdf_tril_copy_f64(const double* a, int lda, long long stride_a, double* out, int ldo, long long stride_o, int d, int count,
+                      int transpose, void* stream);
+int cdf_logdet_diag_f64(const double* m, int ld, long long stride, int d, int count, double* out, void* stream);
+int cdf_gmm_center_scale_f64(const void* x, int x_is_f64, int ldx, int n, int d, const double* mean, const double* resp, const double* nk,
+                             double* z, int ldz, double* zt, int ldzt, void* stream);
+int cdf_rowsumsq_f64(const double* y, int ldy, int n, int d, double* out, void* stream);
+int cdf_gmm_resp_blocks(int n);
+int cdf_gmm_resp_f64(const double* maha, int ldm, const double* logdet, const double* logw, int n, int d, int K, int hard, double* resp,
+                     int ldr, double* nk, double* lse_sum, double* partial, void* stream);
 
 /* parameter layout <-> GEMM layout: dst[t][r][c] = src[c*s_c + r*s_r + t*s_t] (c >= C zero-filled up to ldc);
  * g[c*s_c + r*s_r + t*s_t] (+)= sum_z ws[z][t][r][c] */
