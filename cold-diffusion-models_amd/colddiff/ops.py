@@ -460,48 +460,46 @@ def wgrad_into(gparam, wplan, xa, CA, xb, CB, s_t, s_r, s_c, gbias=None, xa_s=No
     B = xa.shape[0]
     M = B * wplan.QH * wplan.QW
     ldo = r4(CB)
+    geom = (B, wplan.QH, wplan.QW, wplan.HA, wplan.WA, wplan.sa, wplan.HB, wplan.WB, wplan.sb, CA, CB, wplan.ntaps, wplan.desc)
+    def side(C):                                  # tiles along a side (a 64-channel side gets a 64-wide tile)
+        return 1 if C <= 64 else (C + 127) // 128
+    # each route sets the split count ns and launch(ws, bsum, S), which is called right below with xa / xb / ns as they stand then; the slabs,
+    # the bias partials and their reduction follow in one place
     if xa_s is not None and xb_s is not None and CA >= 64 and CB >= 64 and M >= WGRAD_SP_MIN_M:
         # both operands already split into bf16 hi/lo planes: copy + MFMA only (64-wide tiles for 64-channel sides);
         # xa / xb themselves may be shape-only stand-ins here
-        dev = xa_s[0].device
+        src = xa_s[0]
         ntap_blocks = (wplan.ntaps + 1) // 2 if (CA <= 64 < CB and wplan.same_b) else wplan.ntaps    # two taps per tile there
         slots = 512
         if L.cdf_conv_wgrad_bf16x_is_row3(wplan.QH, wplan.QW, CA, CB, wplan.ntaps, 1 if wplan.same3x3 else 0, rt.tune_ptr()):
             ntap_blocks, slots = 3, 256                                # one block per row of taps, one 512-thread block per CU
-        tiles = (1 if CA <= 64 else (CA + 127) // 128) * (1 if CB <= 64 else (CB + 127) // 128) * ntap_blocks
-        ns = best_nsplit(tiles, slots, M // 512)
-        ws = torch.empty((ns, wplan.ntaps, CA, ldo), device=dev, dtype=torch.float32)
-        S = rt.stream(xa_s[0])
-        bsum = torch.empty((ns, ldo), device=dev, dtype=torch.float32) if gbias is not None else None
-        L.cdf_conv_wgrad_bf16x(P(xa_s[0]), P(xa_s[1]), ld_of(xa_s[0]), P(xb_s[0]), P(xb_s[1]), ld_of(xb_s[0]), P(zero_page(dev)),
-                               P(ws), ldo, B, wplan.QH, wplan.QW, wplan.HA, wplan.WA, wplan.sa, wplan.HB, wplan.WB, wplan.sb, CA, CB,
-                               wplan.ntaps, wplan.desc, ns, P(bsum), rt.tune_ptr(), S)
-        _reduce_slabs(L, ws, gparam, ns, wplan.ntaps, CA, CB, ldo, s_t, s_r, s_c, bsum, gbias, S)
-        return
-    # (bf16 activation storage: the operands of a layer too thin for the plane kernel above are widened for the kernels below)
-    xa, xb = f32_of(xa, CA), f32_of(xb, CB)
-    if rt.precision != "f32" and CA >= 128 and CB >= 128 and M >= WGRAD_SP_MIN_M:   # full 128x128 tiles only; thinner layers are faster on the fp32 kernel
-        # split-precision bf16 MFMA kernel: 128x128 tiles, resident twice per CU (512 slots)
-        tiles = ((CA + 127) // 128) * ((CB + 127) // 128) * wplan.ntaps
-        # (a block of this kernel walks its pixels in dependent 32-pixel steps of ~4 us each -- load, split, transposing LDS pass, MFMA --
-        #  so a thin layer at 16 x 16 pixels took 70 us for 1 GFLOP with M // 512 = 16 splits: splits down to _SP_WGRAD_MIN_PIX pixels)
-        ns = best_nsplit(tiles, 512, max(1, M // _SP_WGRAD_MIN_PIX))
-        ws = torch.empty((ns, wplan.ntaps, CA, ldo), device=xa.device, dtype=torch.float32)
-        S = rt.stream(xa)
-        bsum = torch.empty((ns, ldo), device=xa.device, dtype=torch.float32) if gbias is not None else None
-        L.cdf_conv_wgrad_bf16(P(xa), ld_of(xa), P(xb), ld_of(xb), P(ws), ldo, B, wplan.QH, wplan.QW, wplan.HA, wplan.WA, wplan.sa,
-                              wplan.HB, wplan.WB, wplan.sb, CA, CB, wplan.ntaps, wplan.desc, ns, P(bsum), S)
-        _reduce_slabs(L, ws, gparam, ns, wplan.ntaps, CA, CB, ldo, s_t, s_r, s_c, bsum, gbias, S)
-        return
-    tiles_f32 = (1 if CA <= 64 else (CA + 127) // 128) * (1 if CB <= 64 else (CB + 127) // 128) * wplan.ntaps
-    # (one or two output tiles -- 64 -> 3, the 64-channel k|v projection: a block keeps ONE 4 KB chunk in flight, so the bandwidth
-    #  comes from filling all 1024 block slots: up to 1024 splits there, the slabs stay a few percent of the operand bytes)
-    ns = best_nsplit(tiles_f32, 1024, max(1, M // 256), cap=1024 if tiles_f32 <= 2 else 256)
-    ws = torch.empty((ns, wplan.ntaps, CA, ldo), device=xa.device, dtype=torch.float32)
-    S = rt.stream(xa)
-    bsum = torch.empty((ns, ldo), device=xa.device, dtype=torch.float32) if gbias is not None else None
-    L.cdf_conv_wgrad(P(xa), ld_of(xa), P(xb), ld_of(xb), P(ws), ldo, B, wplan.QH, wplan.QW, wplan.HA, wplan.WA, wplan.sa,
-                     wplan.HB, wplan.WB, wplan.sb, CA, CB, wplan.ntaps, wplan.desc, ns, 1, 0, 0, 0, P(bsum), S)
+        ns = best_nsplit(side(CA) * side(CB) * ntap_blocks, slots, M // 512)
+        def launch(ws, bsum, S):
+            L.cdf_conv_wgrad_bf16x(P(xa_s[0]), P(xa_s[1]), ld_of(xa_s[0]), P(xb_s[0]), P(xb_s[1]), ld_of(xb_s[0]), P(zero_page(src.device)),
+                                   P(ws), ldo, *geom, ns, P(bsum), rt.tune_ptr(), S)
+    else:
+        # (bf16 activation storage: the operands of a layer too thin for the plane kernel above are widened for the kernels below)
+        xa, xb = f32_of(xa, CA), f32_of(xb, CB)
+        src = xa
+        if rt.precision != "f32" and CA >= 128 and CB >= 128 and M >= WGRAD_SP_MIN_M:   # full 128x128 tiles only; thinner layers are faster on the fp32 kernel
+            # split-precision bf16 MFMA kernel: 128x128 tiles, resident twice per CU (512 slots)
+            tiles = ((CA + 127) // 128) * ((CB + 127) // 128) * wplan.ntaps
+            # (a block of this kernel walks its pixels in dependent 32-pixel steps of ~4 us each -- load, split, transposing LDS pass, MFMA --
+            #  so a thin layer at 16 x 16 pixels took 70 us for 1 GFLOP with M // 512 = 16 splits: splits down to _SP_WGRAD_MIN_PIX pixels)
+            ns = best_nsplit(tiles, 512, max(1, M // _SP_WGRAD_MIN_PIX))
+            def launch(ws, bsum, S):
+                L.cdf_conv_wgrad_bf16(P(xa), ld_of(xa), P(xb), ld_of(xb), P(ws), ldo, *geom, ns, P(bsum), S)
+        else:
+            tiles_f32 = side(CA) * side(CB) * wplan.ntaps
+            # (one or two output tiles -- 64 -> 3, the 64-channel k|v projection: a block keeps ONE 4 KB chunk in flight, so the bandwidth
+            #  comes from filling all 1024 block slots: up to 1024 splits there, the slabs stay a few percent of the operand bytes)
+            ns = best_nsplit(tiles_f32, 1024, max(1, M // 256), cap=1024 if tiles_f32 <= 2 else 256)
+            def launch(ws, bsum, S):
+                L.cdf_conv_wgrad(P(xa), ld_of(xa), P(xb), ld_of(xb), P(ws), ldo, *geom, ns, 1, 0, 0, 0, P(bsum), S)
+    ws = torch.empty((ns, wplan.ntaps, CA, ldo), device=src.device, dtype=torch.float32)
+    S = rt.stream(src)
+    bsum = torch.empty((ns, ldo), device=src.device, dtype=torch.float32) if gbias is not None else None
+    launch(ws, bsum, S)
     _reduce_slabs(L, ws, gparam, ns, wplan.ntaps, CA, CB, ldo, s_t, s_r, s_c, bsum, gbias, S)
 
 

@@ -29,6 +29,17 @@ __device__ __forceinline__ bf16x4_v cdf_lds_read_tr16(const unsigned short* p) {
     return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) bf16x4_v*)p);
 }
 #endif
+// One operand's MFMA fragment out of a pixel-major tile: 8 consecutive pixels (two transposing reads, 4 rows apart) of the lane's channel, hi
+// plane and -- NS == 3 -- the lo plane `plane` elements behind it.
+template <int NS>
+__device__ __forceinline__ void cdf_tr_frag(const unsigned short* p, int plane, int pitch, bf16x8_v& hi, bf16x8_v& lo) {
+    const bf16x4_v h0 = cdf_lds_read_tr16(p), h1 = cdf_lds_read_tr16(p + 4 * pitch);
+    hi = __builtin_shufflevector(h0, h1, 0, 1, 2, 3, 4, 5, 6, 7);
+    if constexpr (NS == 3) {
+        const bf16x4_v l0 = cdf_lds_read_tr16(p + plane), l1 = cdf_lds_read_tr16(p + plane + 4 * pitch);
+        lo = __builtin_shufflevector(l0, l1, 0, 1, 2, 3, 4, 5, 6, 7);
+    }
+}
 
 // Block tile BM x BN, WM x WN waves of (BM/WM) x (BN/WN): the whole tile goes through LDS in one pass (cdf_epilogue.h).
 constexpr int CDF_SP_CPITCH = 136;

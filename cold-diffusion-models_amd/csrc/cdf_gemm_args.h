@@ -1,6 +1,6 @@
 // cdf_gemm_args.h -- host-side marshalling the gather-GEMM entry points share: the phase record of the kernel argument structs and its
-// parser, the filler of the fields ConvArgs (k_conv.hip), SpArgs and SpxArgs (cdf_conv_sp.h) have in common, the geometry filler of the
-// weight-gradient argument structs.  The structs themselves stay apart: their layout is the kernels' kernarg layout.
+// parser, the filler of the fields ConvArgs (k_conv.hip), SpArgs and SpxArgs (cdf_conv_sp.h) have in common.  The structs themselves
+// stay apart: their layout is the kernels' kernarg layout.  (The weight-gradient argument structs' geometry filler: cdf_wgrad.h.)
 #pragma once
 #include "cdf_common.h"
 #include "cdf_epilogue.h"
@@ -46,22 +46,4 @@ template <class Args>
 static inline void cdf_clear_epi(Args& a) {
     a.epi = 0;
     a.ln_x = nullptr; a.ln_mean = nullptr; a.ln_rstd = nullptr; a.ln_part = nullptr; a.ld_lnx = 0;
-}
-
-// Geometry, tap table (tap_desc: per tap [day, dax, dby, dbx]) and split of a weight-gradient launch; bk = the kernel's pixels per K step
-// (a split is a whole number of steps).
-template <class Args>
-static inline int cdf_fill_wgrad_geom(Args& a, const char* who, int B, int QH, int QW, int HA, int WA, int sa, int HB, int WB, int sb, int CA,
-                                      int CB, int ntaps, const int* tap_desc, int nsplit, int bk) {
-    CDF_REQUIRE(ntaps >= 1 && ntaps <= CDF_MAX_TAPS && tap_desc && nsplit >= 1, "%s: bad tap / split count", who);
-    a.B = B; a.QH = QH; a.QW = QW; a.HA = HA; a.WA = WA; a.sa = sa; a.HB = HB; a.WB = WB; a.sb = sb;
-    a.CA = CA; a.CB = CB; a.ntaps = ntaps; a.nsplit = nsplit;
-    a.m_per_split = cdf_cdiv(cdf_cdiv(B * QH * QW, nsplit), bk) * bk;
-    for (int t = 0; t < ntaps; ++t) {
-        a.day[t] = (signed char)tap_desc[4 * t + 0];
-        a.dax[t] = (signed char)tap_desc[4 * t + 1];
-        a.dby[t] = (signed char)tap_desc[4 * t + 2];
-        a.dbx[t] = (signed char)tap_desc[4 * t + 3];
-    }
-    return CDF_OK;
 }

@@ -19,7 +19,7 @@
 // The MFMA k index is free as long as A and B agree, so lane half h owns k = 8h..8h+7 of the
 // chunk: its A fragment is two ds_read_b128 (row stride 20 floats -> conflict-free).
 #include <atomic>
-#include "cdf_gemm_args.h"
+#include "cdf_wgrad.h"
 #include "colddiff.h"
 
 struct ConvArgs {
@@ -231,7 +231,7 @@ __global__ void __launch_bounds__(256, 4) conv_igemm_kernel(ConvArgs a) {
 // ------------------------------------------------------------------------------------------------
 // wgrad: out[z][tap][ca][cb] = sum_{m in split z} XA[pixA(m,tap)][ca] * XB[pixB(m,tap)][cb]
 // m = (b, qy, qx); pixA = (qy*sa + day, qx*sa + dax) in [HA,WA]; pixB likewise. Rows with an
-// out-of-range pixel on either side contribute zero.
+// out-of-range pixel on either side contribute zero.  The kernel keeps its own text around the K loop (cdf_wgrad.h says why).
 // ------------------------------------------------------------------------------------------------
 struct WgradArgs {
     const float* xa;

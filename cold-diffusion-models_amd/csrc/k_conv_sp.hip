@@ -14,6 +14,7 @@
 //   * activations stay fp32 in HBM and are split while being written to LDS (VALU work hidden under MFMA);
 //   * BK = 32, LDS rows are 40 bf16 (80 B) so that every ds_read_b128 fragment read is conflict-free.
 #include "cdf_conv_sp.h"
+#include "cdf_wgrad.h"
 #include <atomic>
 
 // 256 threads = 4 waves (2x2), block tile 128x128, wave tile 64x64 = 2x2 MFMA 32x32 tiles.
@@ -180,7 +181,7 @@ __global__ void __launch_bounds__(256, 2) conv_igemm_sp_kernel(SpArgs a) {
 // The contraction runs over PIXELS, which are the slow index of both NHWC operands, so the LDS tiles
 // stay pixel-major ([32 px][128 ch] bf16 hi / lo, split while being stored) and each lane assembles
 // its 8-pixel MFMA fragment from eight 16-bit LDS reads (32 consecutive channels per half-wave:
-// conflict-free).  Tile 128 (ca) x 128 (cb), BK = 32 pixels, 4 waves of 64x64.
+// conflict-free).  Tile 128 (ca) x 128 (cb), BK = 32 pixels, 4 waves of 64x64.  Block range, pixel walk, bias-gradient fold: cdf_wgrad.h.
 // ------------------------------------------------------------------------------------------------
 struct SpWgradArgs {
     const float* xa;
@@ -204,30 +205,17 @@ __global__ void __launch_bounds__(256, 2) conv_wgrad_sp_kernel(SpWgradArgs a) {
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1;
-    const int tiles_b = (a.CB + BC - 1) / BC;
-    int bx, by, bz;
-    cdf_wgrad_block(a.xcd_swizzle, bx, by, bz);
-    const int tile_a = bx / tiles_b, tile_b = bx - tile_a * tiles_b;
-    const int tap = by, split = bz;
-    const int M = a.B * a.QH * a.QW;
-    const int m_lo = split * a.m_per_split;
-    int m_hi = m_lo + a.m_per_split;
-    if (m_hi > M) m_hi = M;
-    const int niter = m_hi > m_lo ? (m_hi - m_lo + BK - 1) / BK : 0;
+    const CdfWgradRange g = cdf_wgrad_range<BK, BC>(a, a.xcd_swizzle);
+    const int tile_a = g.tile_a, tile_b = g.tile_b, tap = g.tap, m_lo = g.m_lo, m_hi = g.m_hi, niter = g.niter;
     const int day = a.day[tap], dax = a.dax[tap], dby = a.dby[tap], dbx = a.dbx[tap];
 
     // load slots: pixel k = (tid >> 5) + 8 p, channel quad c4 = tid & 31 (both operands)
     const int c4 = (tid & 31) * 4;
+    const CdfPixelWalk<BK> walk(a);
     int q[4][3];
 #pragma unroll
-    for (int p = 0; p < 4; ++p) {
-        const int m = m_lo + (tid >> 5) + 8 * p;
-        q[p][0] = m % a.QW;
-        const int t2 = m / a.QW;
-        q[p][1] = t2 % a.QH;
-        q[p][2] = t2 / a.QH;
-    }
-    const bool do_bsum = a.bsum != nullptr && tile_a == 0 && tap == 0;
+    for (int p = 0; p < 4; ++p) walk.decode(m_lo + (tid >> 5) + 8 * p, q[p]);
+    const bool do_bsum = g.bsum(a);
     float4 bs_acc[4];
 #pragma unroll
     for (int p = 0; p < 4; ++p) bs_acc[p] = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -252,11 +240,7 @@ __global__ void __launch_bounds__(256, 2) conv_wgrad_sp_kernel(SpWgradArgs a) {
             const float4 va = *(const float4*)pa, vb = *(const float4*)pb;
             ra[p] = aok ? va : make_float4(0.f, 0.f, 0.f, 0.f);
             rb[p] = bok2 ? vb : make_float4(0.f, 0.f, 0.f, 0.f);
-            q[p][0] += BK;
-            while (q[p][0] >= a.QW) {
-                q[p][0] -= a.QW;
-                if (++q[p][1] >= a.QH) { q[p][1] = 0; ++q[p][2]; }
-            }
+            walk.advance(q[p]);
             if (do_bsum) {
                 bs_acc[p].x += rb[p].x; bs_acc[p].y += rb[p].y; bs_acc[p].z += rb[p].z; bs_acc[p].w += rb[p].w;
             }
@@ -323,15 +307,9 @@ __global__ void __launch_bounds__(256, 2) conv_wgrad_sp_kernel(SpWgradArgs a) {
         float* red = (float*)smem;                 // [32 px][128] floats = 16 KB (stage 0 is idle now)
 #pragma unroll
         for (int p = 0; p < 4; ++p) *(float4*)(red + ((tid >> 5) + 8 * p) * BC + c4) = bs_acc[p];
-        __syncthreads();
-        for (int c = tid; c < BC; c += 256) {
-            float t = 0.f;
-            for (int k = 0; k < BK; ++k) t += red[k * BC + c];
-            const int cc = tile_b * BC + c;
-            if (cc < a.ldo) a.bsum[(long long)split * a.ldo + cc] = cc < a.CB ? t : 0.f;
-        }
+        cdf_wgrad_bsum_fold<BK, BC, 256>(a, red, tile_b, g.split, tid);
     }
-    float* O = a.out + ((long long)split * a.ntaps + tap) * a.CA * a.ldo;
+    float* O = cdf_wgrad_slab(a, g.split, tap);
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll

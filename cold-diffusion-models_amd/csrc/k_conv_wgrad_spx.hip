@@ -1,6 +1,8 @@
 #include "cdf_conv_sp.h"
+#include "cdf_wgrad.h"
 
-// weight gradient with both operands pre-split ([pixels][ld] bf16 hi / lo planes)
+// weight gradient with both operands pre-split ([pixels][ld] bf16 hi / lo planes).  Block range, pixel walk, bias-gradient fold and pad
+// zeroing are the family's (cdf_wgrad.h); the transposing fragment read is cdf_tr_frag (cdf_conv_sp.h).
 
 template <int NS>
 __device__ __forceinline__ void cdf_bf16x8_accum(float* acc8, const u32x4_v& h, const u32x4_v& l) {
@@ -47,16 +49,9 @@ __global__ void __launch_bounds__(256, 2) conv_wgrad_spx_kernel(SpxWgradArgs a) 
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1;
-    const int tiles_b = (a.CB + TB - 1) / TB;
-    int bx, by, bz;
-    cdf_wgrad_block(a.xcd_swizzle, bx, by, bz);
-    const int tile_a = bx / tiles_b, tile_b = bx - tile_a * tiles_b;
-    const int tap = STACK2 ? 2 * by : by, split = bz;
-    const int M = a.B * a.QH * a.QW;
-    const int m_lo = split * a.m_per_split;
-    int m_hi = m_lo + a.m_per_split;
-    if (m_hi > M) m_hi = M;
-    const int niter = m_hi > m_lo ? (m_hi - m_lo + BK - 1) / BK : 0;
+    const CdfWgradRange g = cdf_wgrad_range<BK, TB>(a, a.xcd_swizzle);
+    const int tile_a = g.tile_a, tile_b = g.tile_b, m_lo = g.m_lo, m_hi = g.m_hi, niter = g.niter;
+    const int tap = STACK2 ? 2 * g.tap : g.tap;
     const int dby = a.dby[tap], dbx = a.dbx[tap];
     // load slots: operand X, pass p: pixel (tid / VPR) + PPP p of the chunk, 16-byte channel column (tid % VPR) * 8
     static_assert(!STACK2 || TA == 128, "tap stacking fills a 128-row A tile with two 64-channel taps");
@@ -66,44 +61,20 @@ __global__ void __launch_bounds__(256, 2) conv_wgrad_spx_kernel(SpxWgradArgs a) 
     const int day = a.day[tap_ok ? tap_l : tap], dax = a.dax[tap_ok ? tap_l : tap];
     const int ca = STACK2 ? ((tid % SA::VPR) & 7) * 8 : tile_a * TA + (tid % SA::VPR) * 8;
     const int cb = tile_b * TB + (tid % SB::VPR) * 8;
+    const CdfPixelWalk<BK> walk(a);
     int qa[SA::PASS][3], qb[SB::PASS][3];
 #pragma unroll
-    for (int p = 0; p < SA::PASS; ++p) {
-        const int m = m_lo + tid / SA::VPR + SA::PPP * p;
-        qa[p][0] = m % a.QW;
-        const int t2 = m / a.QW;
-        qa[p][1] = t2 % a.QH;
-        qa[p][2] = t2 / a.QH;
-    }
+    for (int p = 0; p < SA::PASS; ++p) walk.decode(m_lo + tid / SA::VPR + SA::PPP * p, qa[p]);
 #pragma unroll
-    for (int p = 0; p < SB::PASS; ++p) {
-        const int m = m_lo + tid / SB::VPR + SB::PPP * p;
-        qb[p][0] = m % a.QW;
-        const int t2 = m / a.QW;
-        qb[p][1] = t2 % a.QH;
-        qb[p][2] = t2 / a.QH;
-    }
-    const bool do_bsum = a.bsum != nullptr && tile_a == 0 && tap == 0;
+    for (int p = 0; p < SB::PASS; ++p) walk.decode(m_lo + tid / SB::VPR + SB::PPP * p, qb[p]);
+    const bool do_bsum = g.bsum(a);
     float bs_acc[SB::PASS][8];
 #pragma unroll
     for (int p = 0; p < SB::PASS; ++p)
 #pragma unroll
         for (int e = 0; e < 8; ++e) bs_acc[p][e] = 0.f;
 
-    // Everything below is straight-line code on purpose: a divergent branch or loop between the loads makes hipcc
-    // wait for the loads already in flight before it (measured: the prefetch of a chunk degenerates into four
-    // dependent round trips).  The (qx, qy, b) carry uses an exact float reciprocal: q + 0.5 is never a multiple
-    // of the divisor and both stay tiny (q < QW + 32), so the truncation is exact.
-    const float rcp_qw = 1.0f / (float)a.QW, rcp_qh = 1.0f / (float)a.QH;
-    auto advance = [&](int* q) {
-        const int x = q[0] + BK;
-        const int cx = (int)(((float)x + 0.5f) * rcp_qw);
-        q[0] = x - cx * a.QW;
-        const int y = q[1] + cx;
-        const int cy = (int)(((float)y + 0.5f) * rcp_qh);
-        q[1] = y - cy * a.QH;
-        q[2] += cy;
-    };
+    // Everything below is straight-line code on purpose, the (qx, qy, b) carry included (CdfPixelWalk::advance).
     u32x4_v rah[SA::PASS], ral[SA::PASS], rbh[SB::PASS], rbl[SB::PASS];   // (arrays of HIP uint4 structs would live in scratch)
     auto load_global = [&](int it) {
         const int m0 = m_lo + it * BK;
@@ -118,7 +89,7 @@ __global__ void __launch_bounds__(256, 2) conv_wgrad_spx_kernel(SpxWgradArgs a) 
             const size_t off = (size_t)pix * (unsigned)a.lda + (unsigned)ca;
             rah[p] = *(const u32x4_v*)(ok ? a.a_hi + off : a.zero);
             if constexpr (NS == 3) ral[p] = *(const u32x4_v*)(ok ? a.a_lo + off : a.zero);
-            advance(qa[p]);
+            walk.advance(qa[p]);
         }
 #pragma unroll
         for (int p = 0; p < SB::PASS; ++p) {
@@ -129,7 +100,7 @@ __global__ void __launch_bounds__(256, 2) conv_wgrad_spx_kernel(SpxWgradArgs a) 
             const size_t off = (size_t)pix * (unsigned)a.ldb + (unsigned)cb;
             rbh[p] = *(const u32x4_v*)(ok ? a.b_hi + off : a.zero);
             if constexpr (NS == 3) rbl[p] = *(const u32x4_v*)(ok ? a.b_lo + off : a.zero);
-            advance(qb[p]);
+            walk.advance(qb[p]);
         }
     };
     auto store_lds = [&](int buf) {
@@ -173,23 +144,11 @@ __global__ void __launch_bounds__(256, 2) conv_wgrad_spx_kernel(SpxWgradArgs a) 
             bf16x8_v ah[MT], al[MT], bh[NT], bl[NT];
 #pragma unroll
             for (int i = 0; i < MT; ++i) {
-                const unsigned short* pa = sa + tra + ks * 16 * SA::PITCH + i * 32;
-                const bf16x4_v h0 = cdf_lds_read_tr16(pa), h1 = cdf_lds_read_tr16(pa + 4 * SA::PITCH);
-                ah[i] = __builtin_shufflevector(h0, h1, 0, 1, 2, 3, 4, 5, 6, 7);
-                if constexpr (NS == 3) {
-                    const bf16x4_v l0 = cdf_lds_read_tr16(pa + PLANE_A), l1 = cdf_lds_read_tr16(pa + PLANE_A + 4 * SA::PITCH);
-                    al[i] = __builtin_shufflevector(l0, l1, 0, 1, 2, 3, 4, 5, 6, 7);
-                }
+                cdf_tr_frag<NS>(sa + tra + ks * 16 * SA::PITCH + i * 32, PLANE_A, SA::PITCH, ah[i], al[i]);
             }
 #pragma unroll
             for (int j = 0; j < NT; ++j) {
-                const unsigned short* pb = sb + trb + ks * 16 * SB::PITCH + j * 32;
-                const bf16x4_v h0 = cdf_lds_read_tr16(pb), h1 = cdf_lds_read_tr16(pb + 4 * SB::PITCH);
-                bh[j] = __builtin_shufflevector(h0, h1, 0, 1, 2, 3, 4, 5, 6, 7);
-                if constexpr (NS == 3) {
-                    const bf16x4_v l0 = cdf_lds_read_tr16(pb + PLANE_B), l1 = cdf_lds_read_tr16(pb + PLANE_B + 4 * SB::PITCH);
-                    bl[j] = __builtin_shufflevector(l0, l1, 0, 1, 2, 3, 4, 5, 6, 7);
-                }
+                cdf_tr_frag<NS>(sb + trb + ks * 16 * SB::PITCH + j * 32, PLANE_B, SB::PITCH, bh[j], bl[j]);
             }
 #pragma unroll
             for (int i = 0; i < MT; ++i)
@@ -208,20 +167,14 @@ __global__ void __launch_bounds__(256, 2) conv_wgrad_spx_kernel(SpxWgradArgs a) 
         for (int p = 0; p < SB::PASS; ++p)
 #pragma unroll
             for (int e = 0; e < 8; ++e) red[(tid / SB::VPR + SB::PPP * p) * TB + (tid % SB::VPR) * 8 + e] = bs_acc[p][e];
-        __syncthreads();
-        for (int c = tid; c < TB; c += 256) {
-            float t = 0.f;
-            for (int k = 0; k < BK; ++k) t += red[k * TB + c];
-            const int cc = tile_b * TB + c;
-            if (cc < a.ldo) a.bsum[(long long)split * a.ldo + cc] = cc < a.CB ? t : 0.f;
-        }
+        cdf_wgrad_bsum_fold<BK, TB, 256>(a, red, tile_b, g.split, tid);
         __syncthreads();
     }
     // accumulators -> LDS [TA][TB + 8] -> float4 rows of the split's partial-sum slab (see cdf_epilogue.h)
     constexpr int CP = TB + 8;
     cdf_acc_stage(red, CP, wm * (TA / 2), wn * (TB / 2), acc, half, l31);
     __syncthreads();
-    float* O = a.out + ((long long)split * a.ntaps + tap) * a.CA * a.ldo;
+    float* O = cdf_wgrad_slab(a, g.split, tap);
     constexpr int TPR = TB / 4, RPS = 256 / TPR;
     const int c4 = (tid % TPR) * 4, col = tile_b * TB + c4;
     if (col < a.ldo) {
@@ -232,12 +185,7 @@ __global__ void __launch_bounds__(256, 2) conv_wgrad_spx_kernel(SpxWgradArgs a) 
                 row = (r >> 6) * a.CA + (r & 63);
             } else if (row >= a.CA) break;
             float4 v = *(const float4*)(red + r * CP + c4);
-            if (col + 3 >= a.CB) {                 // zero the pitch padding (ldo % 4 == 0 keeps the store in bounds)
-                if (col + 0 >= a.CB) v.x = 0.f;
-                if (col + 1 >= a.CB) v.y = 0.f;
-                if (col + 2 >= a.CB) v.z = 0.f;
-                v.w = 0.f;
-            }
+            cdf_wgrad_zero_pad(v, col, a.CB);
             *(float4*)(O + (long long)row * a.ldo + col) = v;
         }
     }
@@ -253,6 +201,7 @@ __global__ void __launch_bounds__(256, 2) conv_wgrad_spx_kernel(SpxWgradArgs a) 
 // tile at pixel offsets 0, 1, 2: a third of the loads (and of the per-chunk address arithmetic) per MFMA.  Pixel addresses are
 // linear in the chunk index (no per-tap decode); the row / image borders are a per-lane mask.  8 waves (32 x TB/WB tiles, three
 // accumulator sets), one block per CU; grid (tiles, 3 tap rows, splits) in the XCD-aware order of cdf_wgrad_block.
+// Split range, bias fold and slab store are this kernel's own, kept on a measurement: see cdf_wgrad.h.
 // ================================================================================================
 template <int TA, int TB, int NS = 3>
 __global__ void __launch_bounds__(512, 1) conv_wgrad_row3_kernel(SpxWgradArgs a) {
@@ -375,24 +324,12 @@ __global__ void __launch_bounds__(512, 1) conv_wgrad_row3_kernel(SpxWgradArgs a)
         bf16x8_v bh[NT], bl[NT];
 #pragma unroll
         for (int j = 0; j < NT; ++j) {
-            const unsigned short* q = sb + trb + ks * 16 * PITCH_B + j * 32;
-            const bf16x4_v h0 = cdf_lds_read_tr16(q), h1 = cdf_lds_read_tr16(q + 4 * PITCH_B);
-            bh[j] = __builtin_shufflevector(h0, h1, 0, 1, 2, 3, 4, 5, 6, 7);
-            if constexpr (NS == 3) {
-                const bf16x4_v l0 = cdf_lds_read_tr16(q + PLANE_B), l1 = cdf_lds_read_tr16(q + PLANE_B + 4 * PITCH_B);
-                bl[j] = __builtin_shufflevector(l0, l1, 0, 1, 2, 3, 4, 5, 6, 7);
-            }
+            cdf_tr_frag<NS>(sb + trb + ks * 16 * PITCH_B + j * 32, PLANE_B, PITCH_B, bh[j], bl[j]);
         }
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
-            const unsigned short* q = sa + tra[i] + ks * (16 * PITCH_A + ks_skip);
-            const bf16x4_v h0 = cdf_lds_read_tr16(q), h1 = cdf_lds_read_tr16(q + 4 * PITCH_A);
-            const bf16x8_v ah = __builtin_shufflevector(h0, h1, 0, 1, 2, 3, 4, 5, 6, 7);
-            bf16x8_v al;
-            if constexpr (NS == 3) {
-                const bf16x4_v l0 = cdf_lds_read_tr16(q + PLANE_A), l1 = cdf_lds_read_tr16(q + PLANE_A + 4 * PITCH_A);
-                al = __builtin_shufflevector(l0, l1, 0, 1, 2, 3, 4, 5, 6, 7);
-            }
+            bf16x8_v ah, al;
+            cdf_tr_frag<NS>(sa + tra[i] + ks * (16 * PITCH_A + ks_skip), PLANE_A, PITCH_A, ah, al);
 #pragma unroll
             for (int j = 0; j < NT; ++j) {
                 cdf_mma_sp<NS>(acc[i][j], ah, al, bh[j], bl[j]);
@@ -466,12 +403,7 @@ __global__ void __launch_bounds__(512, 1) conv_wgrad_row3_kernel(SpxWgradArgs a)
                 const int row = tile_a * TA + r;
                 if (row >= a.CA) break;
                 float4 v = *(const float4*)(red + r * CP + c4);
-                if (col + 3 >= a.CB) {             // zero the pitch padding (ldo % 4 == 0 keeps the store in bounds)
-                    if (col + 0 >= a.CB) v.x = 0.f;
-                    if (col + 1 >= a.CB) v.y = 0.f;
-                    if (col + 2 >= a.CB) v.z = 0.f;
-                    v.w = 0.f;
-                }
+                cdf_wgrad_zero_pad(v, col, a.CB);
                 *(float4*)(O + (long long)row * a.ldo + col) = v;
             }
         }
@@ -490,11 +422,17 @@ static int launch_wgrad_spx(const SpxWgradArgs& a, hipStream_t s, CdfPlan* plan)
     return cdf_check_launch("conv_wgrad_spx");
 }
 
+// The geometry test of the row-of-taps kernel, for the query and the dispatcher alike.  same_size: nine taps of a stride-1 convolution whose
+// two operands both have the pixel grid's size (the query is told, the dispatcher looks at its geometry).
+static bool wgrad_row3_geom(const cdf_gemm_tuning& T, int QH, int QW, int CA, int CB, int ntaps, bool same_size) {
+    return T.wgrad_row3 && same_size && ntaps == 9 && (QW == 16 || QW == 32 || QW == 64 || QW == 128) && (QH * QW) % 32 == 0 &&
+           (QW >= 32 || QH % (32 / QW) == 0) && !(CA <= 64 && CB <= 64);
+}
+
 // 1 if cdf_conv_wgrad_bf16x takes the row-of-taps kernel for this geometry (the caller sizes the split count by it:
 // 3 tap blocks per tile and one block per CU instead of 9 (or 5) and two)
 extern "C" int cdf_conv_wgrad_bf16x_is_row3(int QH, int QW, int CA, int CB, int ntaps, int same_size_3x3, const cdf_gemm_tuning* tune) {
-    return cdf_tune(tune)->wgrad_row3 && same_size_3x3 && ntaps == 9 && (QW == 16 || QW == 32 || QW == 64 || QW == 128) && (QH * QW) % 32 == 0 &&
-           (QW >= 32 || QH % (32 / QW) == 0) && !(CA <= 64 && CB <= 64);
+    return wgrad_row3_geom(*cdf_tune(tune), QH, QW, CA, CB, ntaps, same_size_3x3 != 0);
 }
 
 template <int NS, int TA, int TB>
@@ -511,9 +449,10 @@ static int launch_wgrad_row3(const SpxWgradArgs& a, hipStream_t s, CdfPlan* plan
 template <int NS>
 static int dispatch_wgrad_bf16x(SpxWgradArgs& a, int QH, int QW, int HA, int WA, int sa, int HB, int WB, int sb, int CA, int CB, int ntaps,
                                 const cdf_gemm_tuning& T, hipStream_t s, CdfPlan* plan = nullptr) {
-    // 3 x 3 stride-1 "same" convolutions (X shifted per tap, dY read in place): one block per row of taps
-    if (T.wgrad_row3 && ntaps == 9 && sa == 1 && sb == 1 && HA == QH && WA == QW && HB == QH && WB == QW &&
-        (QW == 16 || QW == 32 || QW == 64 || QW == 128) && (QH * QW) % 32 == 0 && (QW >= 32 || QH % (32 / QW) == 0) && !(CA <= 64 && CB <= 64)) {
+    // 3 x 3 stride-1 "same" convolutions (X shifted per tap, dY read in place): one block per row of taps.  The tap table is the only
+    // condition on top of wgrad_row3_geom: row-major taps, A shifted by (-1 .. 1, -1 .. 1), B in place -- what the query's caller promises
+    // with same_size_3x3.
+    if (wgrad_row3_geom(T, QH, QW, CA, CB, ntaps, sa == 1 && sb == 1 && HA == QH && WA == QW && HB == QH && WB == QW)) {
         bool ok = true;
         for (int g = 0; g < 3 && ok; ++g) {
             int seen = 0;

@@ -753,6 +753,8 @@ def test_refusals(be):
     ws.fill_(float("nan")), bsum.fill_(float("nan"))
     _refused(be, "cdf_conv_wgrad", wargs[:5] + (20,) + wargs[6:], [ws, bsum], "a weight gradient with ldo < CB")
     _refused(be, "cdf_conv_wgrad", wargs[:19] + (0,) + wargs[20:], [ws, bsum], "nsplit = 0")
+    _refused(be, "cdf_conv_wgrad", wargs[:8] + (1 << 21,) + wargs[9:], [ws, bsum], "QW past the exact range of the pixel walk")
+    assert "pixel grid" in be.L._dll.cdf_last_error().decode()
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -824,6 +826,10 @@ BGEMM_ROWS += [
        3 * 70 * 24, 0, 24, 70 * 24, 0),
 ]
 WGRAD_ROWS += [WR("conv_wgrad", 2, 12, 12, 136, 24, 3, 1, 1, 3, 1)]
+# The pixel walk on 4 x 4 images (a 16-pixel step: four rows, a whole image), with taps and with one tap (slab by slab).  B = 3, M = 48 in
+# four slabs of 16 | 16 | 16 | none: one step each, the decode alone (a slab of two steps leaves no split of M = 48 without pixels).  B = 5,
+# M = 80 in four slabs of 32 | 32 | 16 | none: the second step of a slab comes out of the advance, over four rows and an image boundary.
+WGRAD_ROWS += [WR("conv_wgrad", B, 4, 4, 56, 136, k, 1, k // 2, 4, 1) for B in (3, 5) for k in (3, 1)]
 WGRAD_BATCHED_ROWS += [
     WB("bgemm_tn 136x136", 3, 96, 136, 136, 136, 0, 96 * 136, 136, 0, 96 * 136, 3, 1, 0),
     WB("bgemm_tn 24x136", 3, 96, 24, 136, 24, 0, 96 * 24, 136, 0, 96 * 136, 3, 1, 0),

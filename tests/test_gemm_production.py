@@ -706,6 +706,33 @@ def test_bench_gemm_reaches_resident_blocks_with_several_tiles():
     assert any(hits)
 
 
+def test_wgrad_row3_query_agrees_with_the_dispatcher(be):
+    """cdf_conv_wgrad_bf16x_is_row3 -- asked the way ops.wgrad_into asks it, same_size_3x3 = the plan's own same3x3 -- against the form
+    cdf_conv_wgrad_bf16x_form's dispatch takes, over the rows of both weight-gradient tables, with the row-of-taps kernel on and off, and at
+    a few geometries on either side of each term of the test.  ops.wgrad_into sizes the split count by the query.  Host side: no launch."""
+    L = be.L
+    extra = [("conv_wgrad", 1, H, W, CA, CB, k, s, pad, 1, 0, 3)
+             for (H, W, k, s, pad) in ((16, 16, 3, 1, 1), (6, 16, 3, 1, 1), (7, 16, 3, 1, 1), (5, 32, 3, 1, 1), (24, 24, 3, 1, 1), (16, 48, 3, 1, 1),
+                                       (32, 32, 3, 2, 1), (32, 32, 1, 1, 0), (16, 16, 3, 1, 0), (256, 256, 3, 1, 1))
+             for (CA, CB) in ((64, 64), (64, 128), (128, 64), (136, 136))]
+    extra += [("convT_wgrad", 1, 16, 16, 128, 128, 4, 2, 1, 1, 0, 3)]
+    seen = set()
+    for row in BENCH_WGRAD + EMU_WGRAD + extra:
+        kind, B, H, W, CA, CB, k, s, pad = row[:9]
+        wp = wgrad_plan(kind, H, W, k, s, pad)
+        for on in (1, 0):
+            old = be.tune.get("wgrad_row3")
+            be.tune.set(wgrad_row3=on)
+            try:
+                q = L.cdf_conv_wgrad_bf16x_is_row3(wp.QH, wp.QW, CA, CB, wp.ntaps, 1 if wp.same3x3 else 0, be.tune.ptr)
+                form = decode(wgrad_form(L, row, be.tune.ptr)[0])["form"]
+            finally:
+                be.tune.set(wgrad_row3=old)
+            assert (q != 0) == (form == 1), (row, on, q, form)
+            seen.add((on, form == 1))
+    assert seen == {(1, True), (1, False), (0, False)}
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("row", BENCH_WGRAD, ids=lambda r: "-".join(map(str, r)))
 def test_wgrad_bench_forms_and_split_counts(row):
@@ -781,6 +808,12 @@ EMU_WGRAD = [
     ("conv_wgrad", 1, 24, 24, 40, 136, 3, 1, 1, 7, 1, 1),        # stacked two-tap form (CA <= 64 < CB), hi-only planes
     ("conv_wgrad", 1, 16, 16, 64, 64, 4, 2, 1, 3, 0, 3),
     ("convT_wgrad", 1, 8, 8, 72, 40, 4, 2, 1, 2, 0, 3),
+    # the pixel walk of the per-tap kernel on 4 x 4 images: one 32-pixel step is eight image rows and two images.  B = 3 (M = 48) in three
+    # slabs of 32 | 16 | none: every slab is a single step, the decode alone places its pixels (at M = 48 a slab of two steps, 64 pixels,
+    # leaves no split without pixels: a split count <= 1).  B = 7 (M = 112) in three slabs of 64 | 48 | none: the second step of either
+    # slab comes out of the advance, which carries over several rows and over an image boundary
+    ("conv_wgrad", 3, 4, 4, 72, 40, 3, 1, 1, 3, 1, 3),
+    ("conv_wgrad", 7, 4, 4, 72, 40, 3, 1, 1, 3, 1, 3),
 ]
 
 

@@ -458,6 +458,10 @@ def _wgrad_rows():
         rows += [WS(kind, 6, n4, n4, 128, 128, k, s, pad, 5, bs), WS(kind, 2, n5, n5, 136, 256, k, s, pad, 2, 0, lda=144, ldb=384),
                  WS(kind, 2, n5, n5, 130, 70, k, s, pad, 1, bs), WS(kind, 2, n8, n8, 256, 136, k, s, pad, 3, bs, lda=384)]
     rows += [WS("conv_wgrad", 1, 36, 36, 128, 128, 3, 1, 1, 9, 1)]   # QW = 36 with taps: nine slabs, 8 of 160 pixels and one of 16
+    # the pixel walk on 4 x 4 images with taps (a 32-pixel step: eight rows, two images).  B = 3, M = 48: slabs 32 | 16 | none, one step each
+    # (the decode alone; a two-step slab would be all of M = 48).  B = 7, M = 112: slabs 64 | 48 | none, the second step of a slab comes out
+    # of the advance, over several rows and an image boundary
+    rows += [WS("conv_wgrad", 3, 4, 4, 136, 128, 3, 1, 1, 3, 1), WS("conv_wgrad", 7, 4, 4, 136, 128, 3, 1, 1, 3, 1)]
     return rows
 
 
