@@ -679,7 +679,8 @@ class DecolorTrainer(Trainer):
         network is fed RGB -- reproduced).  The sampler runs in its ends-only mode and the two metrics accumulate per batch
         (`metrics.PairStats`: one launch per batch, one host read at the end); the four sets are kept, on the device, only for a plain
         fid_func.  A fid_func with `new_stats` (`metrics.DeviceFid`) is fed per batch instead: four `FidStats`, the originals' features
-        computed once, no set kept, three `distance` calls at the end.
+        computed once, no set kept, three `distance` calls at the end; one that also has `kid` (`metrics.DeviceFidKid`) adds
+        `kid_<name>` / `kid_std_<name>` and a printed line after each `fid_<name>`.
         `shard`: under `torch.distributed.run` with W > 1 ranks, rank r runs the batches k with k % W == r of rank 0's permutation (every
         rank still draws its own, so its numpy stream advances as without the keyword), the accumulators are all-reduced at the end, every
         rank returns the same dict and rank 0 prints (fid_func: None or one with `new_stats`).
@@ -748,6 +749,9 @@ class DecolorTrainer(Trainer):
             if fid_func is not None:
                 out[f'fid_{name}'] = fid_func.distance(fstats[0], fstats[k + 1]) if fstats is not None else fid_func(samples=[orig, cands[k]])
                 say(f"The FID of {word} images with original image is {out[f'fid_{name}']}")
+            if hasattr(fid_func, 'kid'):
+                out[f'kid_{name}'], out[f'kid_std_{name}'] = fid_func.kid(fstats[0], fstats[k + 1])
+                say(f"The KID of {word} images with original image is {out[f'kid_{name}']} +- {out[f'kid_std_{name}']}")
             say(f"The RMSE of {word} images with original image is {out[f'rmse_{name}']}")
             say(f"The SSIM of {word} images with original image is {out[f'ssim_{name}']}")
             if fid_func is not None and name != 'blur':

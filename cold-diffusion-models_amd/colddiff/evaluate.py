@@ -173,6 +173,7 @@ class EvalMixin:
         sampled and the directly reconstructed images against the originals.  Returns the numbers the reference prints.
         A fid_func with `new_stats` (`metrics.DeviceFid`) is fed batch by batch -- four `FidStats` with the originals' features computed
         once, RMSE / SSIM through `metrics.PairStats` -- and no image set is kept; any other callable gets the concatenated sets.
+        One that also has `kid` (`metrics.DeviceFidKid`) adds `kid_<name>` / `kid_std_<name>` and a printed line after each `fid_<name>`.
         `shard`: under `torch.distributed.run` with W > 1 ranks, rank r runs the batches k with k % W == r, the accumulators are
         all-reduced at the end, every rank returns the same dict and rank 0 prints (fid_func: None or one with `new_stats`)."""
         rank, world = shard_ranks(shard, fid_func)
@@ -249,6 +250,9 @@ class EvalMixin:
             say(f"The SSIM of {name} images with original image is {out[f'ssim_{name}']}")
             if fid is not None:
                 say(f"The FID of {name} images with original image is {out[f'fid_{name}']}")
+            if hasattr(fid, 'kid'):
+                out[f'kid_{name}'], out[f'kid_std_{name}'] = fid.kid(fstats[0], fstats[k + 1])
+                say(f"The KID of {name} images with original image is {out[f'kid_{name}']} +- {out[f'kid_std_{name}']}")
         if fid is not None:
             say(f"Hence the improvement in FID using sampling is {out['fid_blur'] - out['fid_deblur']}")
             say(f"Hence the improvement in FID using direct sampling is {out['fid_blur'] - out['fid_direct_deblur']}")

@@ -7,6 +7,9 @@
   (cdf_moments_f64; `merge` / `all_reduce` join the accumulators of several ranks, cdf_moments_merge_f64) and both matrix square
   roots by a Newton-Schulz iteration on the fp64 matrix cores (cdf_gemm_f64).  The functions
   of Fid/fid_score.py below them stay as they are; `calculate_frechet_distance` is the fallback when the iteration does not settle.
+* KidStats / kid_distance_device / DeviceFidKid: the Kernel Inception Distance of the same features (the metric torch-fidelity and
+  clean-fid pair with FID; upstream has none) -- the rows kept on the device in fp64, the unbiased polynomial-kernel MMD^2 of every random
+  subset in one launch pair on the fp64 matrix cores (cdf_kid_poly3_f64), torch-fidelity's draws from a private RandomState.
 * FID = Frechet distance between the Gaussians fitted to InceptionV3 activations: the network is colddiff.inception.InceptionV3 (the
   reference's Fid/inception.py on the HIP kernels); its pretrained `pt_inception-2015-12-05` weights are a download upstream and are
   read from a local file here ($COLDDIFF_FID_WEIGHTS / torch hub cache).  Any other feature extractor
@@ -258,7 +261,7 @@ class FidStats:
         rt.check(features)
         if features.dim() == 4:                                   # not yet pooled: global spatial average, as get_activations
             features = features.mean((2, 3))
-        return features.reshape(features.shape[0], -1).float().contiguous()
+        return features.reshape(features.shape[0], math.prod(features.shape[1:])).float().contiguous()      # (-1 is ambiguous for an empty batch)
 
     def add(self, features):
         if self._mu is not None:
@@ -466,3 +469,143 @@ class DeviceFid:
 
     def __call__(self, samples):
         return self.distance(self.stats(samples[0]), self.stats(samples[1]))
+
+
+# -- KID on the device ---------------------------------------------------------------------------------------------------
+def kid_poly3(x, y, ix, iy, gamma=None, coef0=1.0):
+    """out[nsub, 4] = (sxx, syy, sxy, mmd2) per subset of the cubic polynomial kernel k(a, b) = (gamma a.b + coef0)^3 (gamma: 1 / d),
+    in fp64 on the matrix cores (cdf_kid_poly3_f64): x [n1, d], y [n2, d] fp64 row-major, ix / iy [nsub, m] int32 row numbers into
+    x / y -- every one of them must be a row of its matrix, nothing checks them on the device."""
+    assert x.dtype == y.dtype == torch.float64 and x.dim() == y.dim() == 2 and x.shape[1] == y.shape[1]
+    assert x.stride(1) == 1 and y.stride(1) == 1, "kid_poly3 takes row-major feature matrices"
+    assert ix.dtype == iy.dtype == torch.int32 and ix.dim() == 2 and ix.shape == iy.shape and ix.is_contiguous() and iy.is_contiguous()
+    assert x.device == y.device == ix.device == iy.device
+    rt.check(x)
+    (nsub, m), d = ix.shape, x.shape[1]
+    L = rt.lib()
+    partial = torch.empty(nsub * 3 * max(1, L.cdf_kid_tiles(m)), device=x.device, dtype=torch.float64)
+    out = torch.empty((nsub, 4), device=x.device, dtype=torch.float64)
+    L.cdf_kid_poly3_f64(P(x), x.stride(0), P(ix), P(y), y.stride(0), P(iy), nsub, m, d, 1.0 / d if gamma is None else float(gamma),
+                        float(coef0), P(partial), P(out), rt.stream(x))
+    return out
+
+
+class KidStats:
+    """The feature rows of an image set, kept on the device in fp64 for the Kernel Inception Distance: `add(features)` per batch (the
+    inputs of `FidStats.add`; nothing read back), `merge` / `all_reduce` to join the rows of several accumulators or ranks, `rows()` the
+    [n, dims] matrix.  KID draws subsets of rows, so unlike FID it has no running summary: 16 KB per image at dims = 2048."""
+
+    def __init__(self, dims, device):
+        self.dims = int(dims)
+        self.device = torch.device(device)
+        self.n = 0
+        self._chunks = []
+
+    def add(self, features):
+        f = FidStats._rows(features)
+        assert f.shape[1] == self.dims, "KidStats(dims=%d).add: got %d features per row" % (self.dims, f.shape[1])
+        if f.shape[0]:
+            self._chunks.append(f.double())
+            self.n += f.shape[0]
+        return self
+
+    add_images = FidStats.add_images
+
+    def rows(self):
+        if len(self._chunks) != 1:
+            self._chunks = [torch.cat(self._chunks) if self._chunks else torch.empty((0, self.dims), device=self.device, dtype=torch.float64)]
+        return self._chunks[0]
+
+    def merge(self, other):
+        """Appends the rows of `other` (left as it is) below this one's.  -> self"""
+        if other.dims != self.dims:
+            raise ValueError("KidStats(dims=%d).merge: the other rows have dims=%d" % (self.dims, other.dims))
+        if other.n:
+            self._chunks.append(other.rows().to(self.device))
+            self.n += other.n
+        return self
+
+    def all_reduce(self, group=None):
+        """The rows of EVERY rank of `group`, concatenated in rank order, on every rank: the counts are exchanged first and each rank's
+        rows travel padded to the largest, so every rank ends with the same matrix (and the same subsets of it).  Ranks that added nothing
+        take part.  Without a process group, or alone in it, `self` is returned untouched."""
+        world = _group_size(group)
+        if world == 1:
+            return self
+        counts = [int(v) for v in _gather_rows(torch.tensor([float(self.n)], device=self.device, dtype=torch.float64), group)[:, 0].cpu()]
+        if max(counts):
+            mine = torch.zeros(max(counts) * self.dims, device=self.device, dtype=torch.float64)
+            mine[:self.n * self.dims] = self.rows().reshape(-1)
+            parts = _gather_rows(mine, group)
+            self._chunks = [torch.cat([parts[r, :c * self.dims].view(c, self.dims) for r, c in enumerate(counts)])]
+            self.n = sum(counts)
+        return self
+
+
+def kid_subset_indices(n1, n2, subsets, m, seed):
+    """The draws of torch-fidelity's `kid`: one `RandomState(seed)`; per subset `choice(n1, m, replace=False)`, then
+    `choice(n2, m, replace=False)`.  numpy's global stream is not touched.  -> (ix, iy) int32 [subsets, m]"""
+    rng = np.random.RandomState(seed)
+    ix, iy = np.empty((subsets, m), dtype=np.int32), np.empty((subsets, m), dtype=np.int32)
+    for s in range(subsets):
+        ix[s] = rng.choice(n1, m, replace=False)
+        iy[s] = rng.choice(n2, m, replace=False)
+    return ix, iy
+
+
+def kid_distance_device(s1, s2, subsets=100, subset_size=1000, seed=2020):
+    """Kernel Inception Distance of two KidStats -> (mean, std) over `subsets` random subsets of `subset_size` rows each (None: the
+    smaller row count) of the unbiased MMD^2 with k(a, b) = (a.b / dims + 1)^3 -- torch-fidelity's estimator, defaults and draw order
+    (`kid_subset_indices`), so the value is comparable with that tool's on the same features.  Every subset in one launch pair
+    (`kid_poly3`), one host read of the `subsets` values."""
+    lo = min(s1.n, s2.n)
+    m = lo if subset_size is None else int(subset_size)
+    if m > lo or m < 2:
+        raise ValueError("kid: subset_size = %d must be at least 2 and at most the smaller row count, min(%d, %d) = %d"
+                         % (m, s1.n, s2.n, lo))
+    assert s1.dims == s2.dims, 'Training and test feature rows have different lengths'
+    assert subsets >= 1
+    x, y = s1.rows(), s2.rows()
+    ix, iy = (torch.from_numpy(z).to(x.device) for z in kid_subset_indices(s1.n, s2.n, subsets, m, seed))
+    vals = kid_poly3(x, y.to(x.device), ix, iy)[:, 3].cpu().numpy()
+    return float(np.mean(vals)), float(np.std(vals))
+
+
+class FidKidStats(FidStats):
+    """A FidStats that also keeps the rows (`kid_stats`, a KidStats): one extractor pass feeds both metrics."""
+
+    def __init__(self, dims, device):
+        super().__init__(dims, device)
+        self.kid_stats = KidStats(dims, device)
+
+    def add(self, features):
+        f = self._rows(features)
+        super().add(f)
+        self.kid_stats.add(f)
+        return self
+
+    def merge(self, other):
+        super().merge(other)
+        self.kid_stats.merge(other.kid_stats)
+        return self
+
+    def all_reduce(self, group=None):
+        super().all_reduce(group)
+        self.kid_stats.all_reduce(group)
+        return self
+
+
+class DeviceFidKid(DeviceFid):
+    """DeviceFid whose `new_stats()` also keep the feature rows: `distance` is the FID as before, `kid(s1, s2) -> (mean, std)` the Kernel
+    Inception Distance of the same two sets (`kid_distance_device` with this object's `kid_subsets`, `kid_subset_size`, `kid_seed`).  The
+    Trainers' sweeps add `kid_<name>` / `kid_std_<name>` beside every `fid_<name>` when their fid_func has `kid`."""
+
+    def __init__(self, model=None, dims=2048, batch_size=50, device='cuda:0', kid_subsets=100, kid_subset_size=1000, kid_seed=2020):
+        super().__init__(model=model, dims=dims, batch_size=batch_size, device=device)
+        self.kid_subsets, self.kid_subset_size, self.kid_seed = kid_subsets, kid_subset_size, kid_seed
+
+    def new_stats(self):
+        return FidKidStats(self.dims, self.device)
+
+    def kid(self, s1, s2):
+        return kid_distance_device(s1.kid_stats, s2.kid_stats, self.kid_subsets, self.kid_subset_size, self.kid_seed)

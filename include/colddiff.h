@@ -28,7 +28,7 @@ extern "C" {
 /* Bumped whenever an exported signature changes incompatibly (rounds 1-3 all answered 1 while arguments were added: `tiled`,
  * `onepass`, `slots`, `tune`).  cdf_abi_version() returns the value the LIBRARY was built with; a binding compares it with the
  * header it was generated from before the first call (colddiff/_lib.py does) -- a mismatched pair would read shifted arguments. */
-#define CDF_ABI_VERSION 13
+#define CDF_ABI_VERSION 14
 
 #define CDF_E_INVALID (-1)
 #define CDF_E_UNSUPPORTED (-2)
@@ -443,6 +443,22 @@ int cdf_rowsumsq_f64(const double* y, int ldy, int n, int d, double* out, void* 
 int cdf_gmm_resp_blocks(int n);
 int cdf_gmm_resp_f64(const double* maha, int ldm, const double* logdet, const double* logw, int n, int d, int K, int hard, double* resp,
                      int ldr, double* nk, double* lse_sum, double* partial, void* stream);
+
+/* Kernel Inception Distance on the device (colddiff/metrics.py KidStats / kid_distance_device): the unbiased MMD^2 with the cubic
+ * polynomial kernel k(a, b) = (gamma a.b + coef0)^3 between nsub random subsets of two fp64 feature sets, on the f64 matrix-core tile form
+ * of cdf_gemm_f64; no Gram matrix goes to memory.
+ * x: rows [*][d], row pitch ldx; ix [nsub][m] (device, ints): subset s of x is Xs = the rows ix[s][0..m) in that order.  y / ldy / iy
+ * likewise (Ys).  EVERY INDEX MUST BE A ROW OF ITS MATRIX: the values cannot be checked on the host and are not checked on the device.
+ *   sxx = sum over positions i != j of k(Xs_i, Xs_j)   (positions, not row numbers: a row named at two positions counts)
+ *   syy = the same on Ys;   sxy = sum over all i, j of k(Xs_i, Ys_j)
+ *   mmd2 = (sxx + syy) / (m (m - 1)) - 2 sxy / (m m)
+ * out [nsub][4] = {sxx, syy, sxy, mmd2} per subset.  partial: nsub * 3 * cdf_kid_tiles(m) doubles of scratch, every one of them written by
+ * the call (cdf_kid_tiles: ceil(m / 64)^2, or 0 for an m the entry point refuses).  No atomics, every reduction in a fixed order: two runs
+ * are bit-identical.  m >= 2, nsub in [1, 65535], d >= 1, ldx >= d, ldy >= d, ceil(m / 64) <= 46340.  An evaluation-time call, never a
+ * training or sampler step's. */
+int cdf_kid_tiles(int m);
+int cdf_kid_poly3_f64(const double* x, int ldx, const int* ix, const double* y, int ldy, const int* iy, int nsub, int m, int d,
+                      double gamma, double coef0, double* partial, double* out, void* stream);
 
 /* parameter layout <-> GEMM layout: dst[t][r][c] = src[c*s_c + r*s_r + t*s_t] (c >= C zero-filled up to ldc);
  * g[c*s_c + r*s_r + t*s_t] (+)= sum_z ws[z][t][r][c] */
