@@ -124,7 +124,7 @@ class GemmTuning:
 
 
 # int-returning entry points that are pure host-side queries (sizes / counts), not status codes
-_QUERY = re.compile(r"(_blocks|_nchunk|_nsplit|_abi_version|_is_device_build|_lds_bytes|_is_row3|_ssim_tiles|_kid_tiles|_pack_entry_bytes|_pack_blocks|_kvctx_parts|_bf16x_ksplit|_lnbwd_ok|_bf16x_form)$")
+_QUERY = re.compile(r"(_blocks|_nchunk|_nsplit|_abi_version|_is_device_build|_lds_bytes|_is_row3|_ssim_tiles|_kid_tiles|_knn_splits|_ball_splits|_pack_entry_bytes|_pack_blocks|_kvctx_parts|_bf16x_ksplit|_lnbwd_ok|_bf16x_form)$")
 
 
 class CdfError(RuntimeError):

@@ -680,7 +680,9 @@ class DecolorTrainer(Trainer):
         (`metrics.PairStats`: one launch per batch, one host read at the end); the four sets are kept, on the device, only for a plain
         fid_func.  A fid_func with `new_stats` (`metrics.DeviceFid`) is fed per batch instead: four `FidStats`, the originals' features
         computed once, no set kept, three `distance` calls at the end; one that also has `kid` (`metrics.DeviceFidKid`) adds
-        `kid_<name>` / `kid_std_<name>` and a printed line after each `fid_<name>`.
+        `kid_<name>` / `kid_std_<name>` and a printed line after each `fid_<name>`; one that has `prdc`
+        (`metrics.DeviceFidKidPrdc`) adds `precision_<name>`, `recall_<name>`, `density_<name>`, `coverage_<name>`, `f_score_<name>` and
+        one more line.
         `shard`: under `torch.distributed.run` with W > 1 ranks, rank r runs the batches k with k % W == r of rank 0's permutation (every
         rank still draws its own, so its numpy stream advances as without the keyword), the accumulators are all-reduced at the end, every
         rank returns the same dict and rank 0 prints (fid_func: None or one with `new_stats`).
@@ -752,6 +754,12 @@ class DecolorTrainer(Trainer):
             if hasattr(fid_func, 'kid'):
                 out[f'kid_{name}'], out[f'kid_std_{name}'] = fid_func.kid(fstats[0], fstats[k + 1])
                 say(f"The KID of {word} images with original image is {out[f'kid_{name}']} +- {out[f'kid_std_{name}']}")
+            if hasattr(fid_func, 'prdc'):
+                prdc = fid_func.prdc(fstats[0], fstats[k + 1])
+                for key in ('precision', 'recall', 'density', 'coverage', 'f_score'):
+                    out[f'{key}_{name}'] = prdc[key]
+                say(f"The precision / recall / density / coverage / F-score of {word} images with original image is "
+                    f"{prdc['precision']} / {prdc['recall']} / {prdc['density']} / {prdc['coverage']} / {prdc['f_score']}")
             say(f"The RMSE of {word} images with original image is {out[f'rmse_{name}']}")
             say(f"The SSIM of {word} images with original image is {out[f'ssim_{name}']}")
             if fid_func is not None and name != 'blur':

@@ -173,7 +173,9 @@ class EvalMixin:
         sampled and the directly reconstructed images against the originals.  Returns the numbers the reference prints.
         A fid_func with `new_stats` (`metrics.DeviceFid`) is fed batch by batch -- four `FidStats` with the originals' features computed
         once, RMSE / SSIM through `metrics.PairStats` -- and no image set is kept; any other callable gets the concatenated sets.
-        One that also has `kid` (`metrics.DeviceFidKid`) adds `kid_<name>` / `kid_std_<name>` and a printed line after each `fid_<name>`.
+        One that also has `kid` (`metrics.DeviceFidKid`) adds `kid_<name>` / `kid_std_<name>` and a printed line after each `fid_<name>`;
+        one that has `prdc` (`metrics.DeviceFidKidPrdc`) adds `precision_<name>`, `recall_<name>`, `density_<name>`, `coverage_<name>`,
+        `f_score_<name>` and one more line.
         `shard`: under `torch.distributed.run` with W > 1 ranks, rank r runs the batches k with k % W == r, the accumulators are
         all-reduced at the end, every rank returns the same dict and rank 0 prints (fid_func: None or one with `new_stats`)."""
         rank, world = shard_ranks(shard, fid_func)
@@ -253,6 +255,12 @@ class EvalMixin:
             if hasattr(fid, 'kid'):
                 out[f'kid_{name}'], out[f'kid_std_{name}'] = fid.kid(fstats[0], fstats[k + 1])
                 say(f"The KID of {name} images with original image is {out[f'kid_{name}']} +- {out[f'kid_std_{name}']}")
+            if hasattr(fid, 'prdc'):
+                prdc = fid.prdc(fstats[0], fstats[k + 1])
+                for key in ('precision', 'recall', 'density', 'coverage', 'f_score'):
+                    out[f'{key}_{name}'] = prdc[key]
+                say(f"The precision / recall / density / coverage / F-score of {name} images with original image is "
+                    f"{prdc['precision']} / {prdc['recall']} / {prdc['density']} / {prdc['coverage']} / {prdc['f_score']}")
         if fid is not None:
             say(f"Hence the improvement in FID using sampling is {out['fid_blur'] - out['fid_deblur']}")
             say(f"Hence the improvement in FID using direct sampling is {out['fid_blur'] - out['fid_direct_deblur']}")

@@ -10,6 +10,9 @@
 * KidStats / kid_distance_device / DeviceFidKid: the Kernel Inception Distance of the same features (the metric torch-fidelity and
   clean-fid pair with FID; upstream has none) -- the rows kept on the device in fp64, the unbiased polynomial-kernel MMD^2 of every random
   subset in one launch pair on the fp64 matrix cores (cdf_kid_poly3_f64), torch-fidelity's draws from a private RandomState.
+* knn_sq / ball_counts / prdc_device / DeviceFidKidPrdc: improved precision and recall (torch-fidelity's `prc`) and density and coverage
+  of the same rows -- k-th-neighbour radii and ball memberships from fp64 Gram tiles consumed in the epilogue (cdf_knn_sq_f64,
+  cdf_ball_counts_f64), no n x n matrix, one host read of four integer sums.
 * FID = Frechet distance between the Gaussians fitted to InceptionV3 activations: the network is colddiff.inception.InceptionV3 (the
   reference's Fid/inception.py on the HIP kernels); its pretrained `pt_inception-2015-12-05` weights are a download upstream and are
   read from a local file here ($COLDDIFF_FID_WEIGHTS / torch hub cache).  Any other feature extractor
@@ -609,3 +612,101 @@ class DeviceFidKid(DeviceFid):
 
     def kid(self, s1, s2):
         return kid_distance_device(s1.kid_stats, s2.kid_stats, self.kid_subsets, self.kid_subset_size, self.kid_seed)
+
+
+# -- precision / recall / density / coverage on the device -------------------------------------------------------------------------------
+def _f64_rows(t, what):
+    assert t.dtype == torch.float64 and t.dim() == 2 and t.stride(1) == 1, "%s takes a row-major fp64 matrix" % what
+    return rt.check(t)
+
+
+def row_norms_sq(x):
+    """|x_j|^2 per row of a row-major fp64 matrix, one fixed-order tree per row (cdf_rowsumsq_f64): the norm vector `knn_sq` and
+    `ball_counts` take, computed once per set and shared by every pass."""
+    _f64_rows(x, "row_norms_sq")
+    out = torch.empty(x.shape[0], device=x.device, dtype=torch.float64)
+    rt.lib().cdf_rowsumsq_f64(P(x), x.stride(0), x.shape[0], x.shape[1], P(out), rt.stream(x))
+    return out
+
+
+def knn_sq(x, k, norms=None):
+    """knn[n, k], ascending: the k smallest squared distances D(x_j, x_l) = max(0, |x_j|^2 + |x_l|^2 - 2 x_j.x_l), l != j, of every row
+    of x [n, d] (fp64, row-major, any row pitch) to the other rows of the set, on the fp64 matrix cores (cdf_knn_sq_f64).  Self is left out
+    by position: a second row with the same values is a neighbour at distance 0.  1 <= k <= 8 and n >= k + 1, else CdfError.
+    `norms`: `row_norms_sq(x)` when the caller has it already."""
+    _f64_rows(x, "knn_sq")
+    n, d = x.shape
+    norms = row_norms_sq(x) if norms is None else norms
+    assert norms.dtype == torch.float64 and norms.shape == (n,) and norms.is_contiguous() and norms.device == x.device
+    L = rt.lib()
+    partial = torch.empty(max(1, L.cdf_knn_splits(n)) * n * max(int(k), 1), device=x.device, dtype=torch.float64)
+    out = torch.empty((n, max(int(k), 0)), device=x.device, dtype=torch.float64)
+    L.cdf_knn_sq_f64(P(x), x.stride(0), n, d, int(k), P(norms), P(partial), P(out), rt.stream(x))
+    return out
+
+
+def ball_counts(a, b, rcol=None, rrow=None, anorm=None, bnorm=None):
+    """(cnt_col, cnt_row), int32 [na] each, for the rows of a [na, d] against the rows of b [nb, d] (fp64, row-major, any row pitch):
+    cnt_col[i] = #{ j : D(a_i, b_j) <= rcol[j] } (rcol [nb]: a radius per row of b), cnt_row[i] = #{ j : D(a_i, b_j) <= rrow[i] } (rrow
+    [na]: a radius per row of a); both from one walk of the Gram tiles (cdf_ball_counts_f64), `None` for the side not asked for.  D is the
+    squared distance of `knn_sq`, `<=` includes ties, no row is left out (a and b are different sets)."""
+    _f64_rows(a, "ball_counts")
+    _f64_rows(b, "ball_counts")
+    assert a.shape[1] == b.shape[1] and a.device == b.device
+    (na, d), nb = a.shape, b.shape[0]
+    anorm = row_norms_sq(a) if anorm is None else anorm
+    bnorm = row_norms_sq(b) if bnorm is None else bnorm
+    for v, rows in ((anorm, na), (bnorm, nb), (rcol, nb), (rrow, na)):
+        assert v is None or (v.dtype == torch.float64 and v.shape == (rows,) and v.is_contiguous() and v.device == a.device)
+    L = rt.lib()
+    partial = torch.empty(max(1, L.cdf_ball_splits(na, nb)) * na * 2, device=a.device, dtype=torch.int32)
+    cnt_col = None if rcol is None else torch.empty(na, device=a.device, dtype=torch.int32)
+    cnt_row = None if rrow is None else torch.empty(na, device=a.device, dtype=torch.int32)
+    L.cdf_ball_counts_f64(P(a), a.stride(0), na, P(anorm), P(b), b.stride(0), nb, P(bnorm), d, P(rcol), P(rrow), P(partial), P(cnt_col),
+                          P(cnt_row), rt.stream(a))
+    return cnt_col, cnt_row
+
+
+def prdc_device(s1, s2, k=3):
+    """Improved precision and recall (Kynkaanniemi et al. 2019; torch-fidelity's `prc`) and density and coverage (Naeem et al. 2020) of
+    two KidStats -- s1 the originals X (n rows), s2 the candidates Y (m rows) -- as dict(precision, recall, density, coverage, f_score).
+    With D the squared Euclidean distance in fp64 and rho_S(j) the k-th smallest D of row j of S to the OTHER rows of S (self left out by
+    position, a duplicate row is a neighbour at 0):
+        precision = #{ i : exists j, D(y_i, x_j) <= rho_X(j) } / m        recall   = #{ j : exists i, D(x_j, y_i) <= rho_Y(i) } / n
+        density   = sum_i #{ j : D(y_i, x_j) <= rho_X(j) } / (k m)        coverage = #{ j : exists i, D(x_j, y_i) <= rho_X(j) } / n
+        f_score   = 2 precision recall / max(precision + recall, 1e-5)
+    `<=` throughout, which is torch-fidelity's choice for precision and recall; Naeem's reference code compares with `<`.  The two differ
+    only where a distance equals a radius exactly.  The counts are integers, so the numbers do not depend on any summation order nor on
+    the order of the rows within either set.  Features must be finite (not checked).
+    Two norm launches, two `knn_sq`, two `ball_counts` -- (Y rows, X columns, rcol = rho_X) for precision and density, (X rows, Y
+    columns, rcol = rho_Y, rrow = rho_X) for recall and coverage -- and ONE host read, of the four integer sums."""
+    k = int(k)
+    if not 1 <= k <= 8 or min(s1.n, s2.n) < k + 1:
+        raise ValueError("prdc: k = %d must be in 1...8 and both sets need at least k + 1 rows (got %d and %d)" % (k, s1.n, s2.n))
+    assert s1.dims == s2.dims, 'Training and test feature rows have different lengths'
+    x = s1.rows()
+    y = s2.rows().to(x.device)
+    nx, ny = row_norms_sq(x), row_norms_sq(y)
+    rho_x = knn_sq(x, k, nx)[:, k - 1].contiguous()
+    rho_y = knn_sq(y, k, ny)[:, k - 1].contiguous()
+    in_x, _ = ball_counts(y, x, rcol=rho_x, anorm=ny, bnorm=nx)                           # per y_i: the X balls it lies in
+    in_y, own = ball_counts(x, y, rcol=rho_y, rrow=rho_x, anorm=nx, bnorm=ny)             # per x_j: the Y balls it lies in; the y in its own
+    sums = torch.stack(((in_x > 0).sum(), in_x.sum(dtype=torch.int64), (in_y > 0).sum(), (own > 0).sum())).cpu().tolist()
+    n, m = s1.n, s2.n
+    precision, density, recall, coverage = sums[0] / m, sums[1] / (k * m), sums[2] / n, sums[3] / n
+    return dict(precision=precision, recall=recall, density=density, coverage=coverage,
+                f_score=2.0 * precision * recall / max(precision + recall, 1e-5))
+
+
+class DeviceFidKidPrdc(DeviceFidKid):
+    """DeviceFidKid with `prdc(s1, s2)`: the dict of `prdc_device` (neighbourhood size `prdc_k`) of the same two sets' rows.  The
+    Trainers' sweeps add `precision_<name>`, `recall_<name>`, `density_<name>`, `coverage_<name>` and `f_score_<name>` after
+    `kid_std_<name>` when their fid_func has `prdc`."""
+
+    def __init__(self, model=None, dims=2048, batch_size=50, device='cuda:0', kid_subsets=100, kid_subset_size=1000, kid_seed=2020, prdc_k=3):
+        super().__init__(model=model, dims=dims, batch_size=batch_size, device=device, kid_subsets=kid_subsets,
+                         kid_subset_size=kid_subset_size, kid_seed=kid_seed)
+        self.prdc_k = prdc_k
+
+    def prdc(self, s1, s2):
+        return prdc_device(s1.kid_stats, s2.kid_stats, self.prdc_k)

@@ -28,7 +28,7 @@ extern "C" {
 /* Bumped whenever an exported signature changes incompatibly (rounds 1-3 all answered 1 while arguments were added: `tiled`,
  * `onepass`, `slots`, `tune`).  cdf_abi_version() returns the value the LIBRARY was built with; a binding compares it with the
  * header it was generated from before the first call (colddiff/_lib.py does) -- a mismatched pair would read shifted arguments. */
-#define CDF_ABI_VERSION 14
+#define CDF_ABI_VERSION 15
 
 #define CDF_E_INVALID (-1)
 #define CDF_E_UNSUPPORTED (-2)
@@ -459,6 +459,36 @@ int cdf_gmm_resp_f64(const double* maha, int ldm, const double* logdet, const do
 int cdf_kid_tiles(int m);
 int cdf_kid_poly3_f64(const double* x, int ldx, const int* ix, const double* y, int ldy, const int* iy, int nsub, int m, int d,
                       double gamma, double coef0, double* partial, double* out, void* stream);
+
+/* The k-NN passes of improved precision / recall (Kynkaanniemi et al. 2019; torch-fidelity's `prc`) and density / coverage (Naeem et al.
+ * 2020) on the device (colddiff/metrics.py knn_sq / ball_counts / prdc_device), on the f64 matrix-core tile form of cdf_gemm_f64; nothing
+ * of size n^2 goes to memory.  X: the first set (the originals, n rows), Y: the second (the candidates, m rows), d features, neighbourhood
+ * size k.  Every comparison is on SQUARED Euclidean distances in fp64; no square root is taken:
+ *   D(a, b) = max(0, (|a|^2 + |b|^2) - 2 a.b)
+ * a.b from the matrix cores; |a|^2 the caller's vector, computed once per row per call in one fixed order by cdf_rowsumsq_f64, so D of a
+ * pair of rows is the same number in whichever tile, call or operand position it is computed.  FEATURES MUST BE FINITE: not checked.
+ *   knn_X[j][0..k) ascending: the k smallest of { D(x_j, x_l) : l != j };   rho_X(j) = knn_X[j][k - 1]     (knn_Y, rho_Y likewise on Y)
+ * Self is left out BY POSITION, not by value: a second row with the same values is a neighbour at distance 0.
+ *   precision = #{ i : exists j, D(y_i, x_j) <= rho_X(j) } / m          recall   = #{ j : exists i, D(x_j, y_i) <= rho_Y(i) } / n
+ *   density   = sum_i #{ j : D(y_i, x_j) <= rho_X(j) } / (k m)          coverage = #{ j : exists i, D(x_j, y_i) <= rho_X(j) } / n
+ *   f_score   = 2 precision recall / max(precision + recall, 1e-5)
+ * `<=` throughout: torch-fidelity's choice for precision and recall; Naeem's reference code has `<`.  They differ on exact ties only.
+ * The counts are integers: all four numbers are independent of summation order and of the order of the rows within either set.
+ *
+ * cdf_knn_sq_f64: knn[n][k] of the rows x [n][d] (row pitch ldx) with norms[n] = |x_j|^2.  partial: cdf_knn_splits(n) * n * k doubles of
+ * scratch.  1 <= k <= 8, n >= k + 1, n <= 2^30, d >= 1, ldx >= d.  The full square is walked (no upper-triangle form).
+ * cdf_ball_counts_f64: for every row i of a [na][d] against the rows of b [nb][d] (anorm / bnorm their |.|^2)
+ *   cnt_col[i] = #{ j < nb : D(a_i, b_j) <= rcol[j] }  (rcol [nb]),     cnt_row[i] = #{ j < nb : D(a_i, b_j) <= rrow[i] }  (rrow [na])
+ * from the same Gram tiles; no self-exclusion (two different sets).  Either radius pointer may be NULL: its output is then not touched
+ * and may be NULL as well.  partial: cdf_ball_splits(na, nb) * na * 2 ints of scratch.  na, nb in [1, 2^30], d >= 1, lda >= d, ldb >= d.
+ * Both: grid (row tiles of 64, S column splits), S = cdf_*_splits, a pure function of the row counts (0 for counts the entry point
+ * refuses); every element of partial and of the outputs is written by the call, no atomics, two runs are bit-identical.  Evaluation-time
+ * calls, never a training or sampler step's. */
+int cdf_knn_splits(int n);
+int cdf_knn_sq_f64(const double* x, int ldx, int n, int d, int k, const double* norms, double* partial, double* knn, void* stream);
+int cdf_ball_splits(int na, int nb);
+int cdf_ball_counts_f64(const double* a, int lda, int na, const double* anorm, const double* b, int ldb, int nb, const double* bnorm, int d,
+                        const double* rcol, const double* rrow, int* partial, int* cnt_col, int* cnt_row, void* stream);
 
 /* parameter layout <-> GEMM layout: dst[t][r][c] = src[c*s_c + r*s_r + t*s_t] (c >= C zero-filled up to ldc);
  * g[c*s_c + r*s_r + t*s_t] (+)= sum_z ws[z][t][r][c] */
