@@ -339,6 +339,20 @@ __device__ __forceinline__ float cdf_group_sum(float v, int width) {
     for (int o = width >> 1; o > 0; o >>= 1) v += __shfl_xor(v, o);
     return v;
 }
+// The fp64 sum of v over a block of 256 threads, the same tree whatever the values (two runs are bit-identical); every thread gets the
+// total.  red = 256 doubles of LDS nobody else is reading.  (Here and not in cdf_f64_tile.h: it knows nothing of the tile form, and four of
+// its five callers -- k_gmm.hip's log det, responsibilities and their fold, k_kid.hip's fold -- are plain reductions without a tile.)
+__device__ __forceinline__ double cdf_block_sum_f64(double* red, double v) {
+    const int tid = threadIdx.x;
+    __syncthreads();                                            // (red may still be read from the previous call)
+    red[tid] = v;
+    for (int o = 128; o > 0; o >>= 1) {
+        __syncthreads();
+        if (tid < o) red[tid] += red[tid + o];
+    }
+    __syncthreads();
+    return red[0];
+}
 
 // counter-based dropout mask (Model2.py:94,124 nn.Dropout; the mask stream is this hash, not torch's Philox): element idx of a
 // [rows][C] map (idx = row * C + c) is kept iff cdf_hash32(seed, idx) >= p * 2^32; kept values are scaled by 1 / (1 - p)

@@ -1,6 +1,6 @@
 // k_fid.hip — FID on the device (the half that was still a host program): the fp64 statistics of feature
 // batches and the fp64 GEMM behind the matrix square roots of the Frechet distance (Fid/fid_score.py:149-283: np.cov of an [N, 2048]
-// host matrix and scipy.linalg.sqrtm of a 2048 x 2048 product).  Both kernels run on v_mfma_f64_16x16x4_f64.
+// host matrix and scipy.linalg.sqrtm of a 2048 x 2048 product).  Both of these kernels run on v_mfma_f64_16x16x4_f64.
 //
 // One tile form for both: 256 threads own a 64 x 64 tile of the result, each wave a 32 x 32 quarter = 2 x 2 MFMA tiles = 16 fp64
 // accumulators (32 VGPRs).  K advances in chunks of 16 through two LDS buffers per operand; both operands are kept [k][column of the
@@ -14,15 +14,17 @@
 // epilogue that adds to the tile it read.  Floor of one call: the read-modify-write of the accumulator's triangle, ~ d^2 * 8 B (half the
 // tiles, read and written) = 17 MB at d = 2048, ~4 us at HBM speed if it were alone -- not the 2 n d^2 = 0.42 GFLOP of a batch of 50.
 // cdf_gemm_f64 at 2048^3: 17.2 GFLOP; each operand element is read by 32 tiles (2 x 1 GB through L2), C written once (34 MB).
+//
+// cdf_moments_merge_f64 (the last kernel of the file) joins two such accumulators; it has moments_f64_kernel's tile ownership and no MFMA.
 #include "cdf_common.h"
-#include "cdf_f64_tile.h"     // FID_T / FID_BK / FID_P, fid_chunk_mma, fid_acc_zero: shared with k_gmm.hip
+#include "cdf_f64_tile.h"     // the tile form that k_gmm.hip, k_kid.hip and k_prdc.hip share; the loaders here are this file's own
 #include "colddiff.h"
 
 // ---- c = alpha a b + diag I --------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) gemm_f64_kernel(const double* A, int lda, const double* B, int ldb, double* C, int ldc, int M, int N,
                                                       int K, double alpha, double diag) {
     __shared__ double sa[2][FID_BK * FID_P], sb[2][FID_BK * FID_P];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wr = wave >> 1, wc = wave & 1;
+    const int tid = threadIdx.x;
     const int m0 = blockIdx.y * FID_T, n0 = blockIdx.x * FID_T;
     // a: thread -> row tid >> 2 of the tile, 4 consecutive k (16 rows x 128 B per wave instruction); written transposed, [k][row]
     const int ar = tid >> 2, ak = (tid & 3) * 4;
@@ -33,54 +35,36 @@ __global__ void __launch_bounds__(256) gemm_f64_kernel(const double* A, int lda,
     double ra[4], rb[4];
     f64x4_t acc[2][2];
     fid_acc_zero(acc);
-    const int nchunk = (K + FID_BK - 1) / FID_BK;
-
-#define FID_GEMM_FETCH(k0)                                                                        \
-    do {                                                                                          \
-        const bool brow = (k0) + bk < K;                                                          \
-        const double* pb = B + (size_t)(brow ? (k0) + bk : 0) * ldb;                              \
-        _Pragma("unroll") for (int q = 0; q < 4; ++q) {                                           \
-            ra[q] = arow && (k0) + ak + q < K ? pa[(k0) + ak + q] : 0.0;                          \
-            rb[q] = brow && n0 + bn + q < N ? pb[n0 + bn + q] : 0.0;                              \
-        }                                                                                         \
-    } while (0)
-#define FID_GEMM_PUT(buf)                                                                         \
-    do {                                                                                          \
-        _Pragma("unroll") for (int q = 0; q < 4; ++q) {                                           \
-            sa[buf][(ak + q) * FID_P + ar] = ra[q];                                               \
-            sb[buf][bk * FID_P + bn + q] = rb[q];                                                 \
-        }                                                                                         \
-    } while (0)
-
-    FID_GEMM_FETCH(0);
-    FID_GEMM_PUT(0);
-    __syncthreads();
-    for (int c = 0; c < nchunk; ++c) {
-        const int cur = c & 1;
-        if (c + 1 < nchunk) FID_GEMM_FETCH((c + 1) * FID_BK);
-        fid_chunk_mma(sa[cur], sb[cur], acc, wr, wc, lane);
-        if (c + 1 < nchunk) FID_GEMM_PUT(cur ^ 1);
-        __syncthreads();                    // chunk c + 1 is complete; every wave is past its reads of buffer `cur`, which chunk c + 2 overwrites
-    }
-#undef FID_GEMM_FETCH
-#undef FID_GEMM_PUT
-
+    fid_k_loop(
+        sa[0], sb[0], (K + FID_BK - 1) / FID_BK, acc,
+        [&](int k0) {
+            const bool brow = k0 + bk < K;
+            const double* pak = pa + k0 + ak;                  // (one address per operand and chunk, the four loads at immediate offsets)
+            const double* pb = B + (size_t)(brow ? k0 + bk : 0) * ldb + n0 + bn;
 #pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int col = n0 + wc * 32 + j * 16 + (lane & 15);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int row = m0 + wr * 32 + i * 16 + (lane >> 4) + 4 * r;
-                if (row < M && col < N) C[(size_t)row * ldc + col] = alpha * acc[i][j][r] + (row == col ? diag : 0.0);
+            for (int q = 0; q < 4; ++q) {
+                ra[q] = arow && k0 + ak + q < K ? pak[q] : 0.0;
+                rb[q] = brow && n0 + bn + q < N ? pb[q] : 0.0;
             }
-        }
+        },
+        [&](int buf) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                sa[buf][(ak + q) * FID_P + ar] = ra[q];
+                sb[buf][bk * FID_P + bn + q] = rb[q];
+            }
+        });
+    fid_tile_each(acc, [&](int r, int c, double v) {
+        const int row = m0 + r, col = n0 + c;
+        if (row < M && col < N) C[(size_t)row * ldc + col] = alpha * v + (row == col ? diag : 0.0);
+    });
 }
 
 // ---- centred moments of a feature batch ------------------------------------------------------------------------------------------
 // grid (T, T), T = ceil(d / 64): block (x = bj, y = bi) owns tile (bi, bj) of `outer` and leaves at once when bi > bj.  The diagonal
 // blocks also own sum[64 bi ... 64 bi + 63]: each thread keeps the column sums of what it loads, 16 k rows are folded through LDS.
+// The K pipeline and the accumulator map are written out here (the text of fid_k_loop / fid_tile_each): on the shared helpers this kernel
+// measured slower at n = 50, d = 2048, the shape every FID batch has (profiles/f64_tile_family_ab.txt).
 __global__ void __launch_bounds__(256) moments_f64_kernel(const float* X, int ldx, int n, int d, const double* pivot, double* sum,
                                                          double* outer, int ldo) {
     const int bi = blockIdx.y, bj = blockIdx.x;
@@ -184,4 +168,62 @@ extern "C" int cdf_gemm_f64(const double* a, int lda, const double* b, int ldb, 
     CDF_REQUIRE(ty <= 65535, "cdf_gemm_f64: m = %d is more than 65535 tiles of 64", m);
     CDF_LAUNCH(gemm_f64_kernel, dim3(tx, ty), dim3(256), 0, CDF_S, a, lda, b, ldb, c, ldc, m, n, k, alpha, diag);
     return cdf_check_launch("gemm_f64");
+}
+
+// ---- merge of two accumulators ---------------------------------------------------------------------------------------------------
+// The step that turns the FID statistics of several ranks into one: accumulator b (cdf_moments_f64's n, pivot, sum, outer) added to
+// accumulator a, re-centred on a's pivot.  With delta = pivot_b - pivot_a and s = sum_b, every row x of b satisfies
+// x - pivot_a = (x - pivot_b) + delta, so over b's n_b rows
+//   sum_i (x - pivot_a)_i                = s_i + n_b delta_i
+//   sum   (x - pivot_a)_i (x - pivot_a)_j = outer_b[i][j] + delta_i s_j + s_i delta_j + n_b delta_i delta_j
+// and both are added to a's.  Plain fp64, one thread per element, no atomics: the result does not depend on the launch.
+//
+// Ownership is moments_f64_kernel's: grid (T, T), T = ceil(d / 64), block (x = bj, y = bi) owns the 64 x 64 tile (bi, bj) of the upper
+// block triangle and leaves at once when bi > bj; a diagonal tile is updated whole and its block also owns sum[64 bi ... + 63].
+// A thread keeps one column of the tile (its delta_j and s_j in registers) and walks 16 rows, so a wave instruction reads or writes 64
+// consecutive doubles of one row: 512 B.  HBM-bound: both triangles are read and a's is written, 3 x d (d + 64) / 2 x 8 B = 52 MB at d = 2048.
+__global__ void __launch_bounds__(256) moments_merge_f64_kernel(double nb, const double* pivot_b, const double* sum_b, const double* outer_b,
+                                                               int ldo_b, const double* pivot_a, double* sum_a, double* outer_a, int ldo_a,
+                                                               int d) {
+    const int bi = blockIdx.y, bj = blockIdx.x;
+    if (bi > bj) return;
+    const int tid = threadIdx.x;
+    const int col = bj * FID_T + (tid & 63), r0 = bi * FID_T + (tid >> 6);
+    if (col < d) {
+        const double dj = pivot_b[col] - pivot_a[col], sj = sum_b[col];
+        // every load of the 16 rows is issued before the first store (32 tile reads in flight per thread); a row past d -- the last tile
+        // row only -- reads row d - 1 of the same tile instead and is not stored
+        double vb[16], va[16], di[16], si[16];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int row = r0 + 4 * r < d ? r0 + 4 * r : d - 1;
+            vb[r] = outer_b[(size_t)row * ldo_b + col];
+            va[r] = outer_a[(size_t)row * ldo_a + col];
+            di[r] = pivot_b[row] - pivot_a[row];
+            si[r] = sum_b[row];
+        }
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int row = r0 + 4 * r;
+            // (di sj + si dj) and nb (di dj) are symmetric in (i, j) bit for bit: a diagonal tile stays symmetric
+            if (row < d) outer_a[(size_t)row * ldo_a + col] = va[r] + (vb[r] + ((di[r] * sj + si[r] * dj) + nb * (di[r] * dj)));
+        }
+    }
+    if (bi == bj && tid < FID_T && col < d)                     // (tid < 64: col = 64 bi + tid, the diagonal block's own 64 entries of sum)
+        sum_a[col] += sum_b[col] + nb * (pivot_b[col] - pivot_a[col]);
+}
+
+extern "C" int cdf_moments_merge_f64(double n_b, const double* pivot_b, const double* sum_b, const double* outer_b, int ldo_b,
+                                     const double* pivot_a, double* sum_a, double* outer_a, int ldo_a, int d, void* stream) {
+    CDF_REQUIRE(pivot_b && sum_b && outer_b && pivot_a && sum_a && outer_a, "cdf_moments_merge_f64: null pointer");
+    CDF_REQUIRE(d > 0, "cdf_moments_merge_f64: d must be at least 1 (got %d)", d);
+    CDF_REQUIRE(ldo_a >= d, "cdf_moments_merge_f64: ldo_a (%d) is smaller than d (%d)", ldo_a, d);
+    CDF_REQUIRE(ldo_b >= d, "cdf_moments_merge_f64: ldo_b (%d) is smaller than d (%d)", ldo_b, d);
+    CDF_REQUIRE(n_b >= 1.0, "cdf_moments_merge_f64: n_b must be at least 1 (got %g)", n_b);
+    CDF_REQUIRE(outer_a != outer_b && sum_a != sum_b, "cdf_moments_merge_f64: accumulator b must not be the accumulator being updated");
+    const int t = cdf_cdiv(d, FID_T);
+    CDF_REQUIRE(t <= 65535, "cdf_moments_merge_f64: d = %d is more than 65535 tiles of 64", d);
+    CDF_LAUNCH(moments_merge_f64_kernel, dim3(t, t), dim3(256), 0, CDF_S, n_b, pivot_b, sum_b, outer_b, ldo_b, pivot_a, sum_a, outer_a,
+               ldo_a, d);
+    return cdf_check_launch("moments_merge_f64");
 }

@@ -12,6 +12,8 @@
 //                        sum handed over through LDS.  d^3 / 3 flops, ceil(d / 64) launches.
 //   the small ones       centre-and-scale (with the transposed copy the covariance GEMM needs), row sums of squares, the responsibilities
 //                        with their two-stage reductions, log det from the diagonal, a triangle copy / transpose.
+// Shared with the other fp64 files: the X Y^T loader and the accumulator walk of cdf_f64_tile.h (trailing update, triangular inverse; the
+// inverse's second product has an MFMA loop of its own) and cdf_common.h's fixed-tree block sum (log det, responsibilities).
 #include <float.h>
 #include <math.h>
 
@@ -23,19 +25,6 @@
 #define GMM_DP 65                 // LDS row pitch of the 64 x 64 diagonal block (odd: a column walk touches every bank pair once)
 
 __device__ __forceinline__ int gmm_min(int a, int b) { return a < b ? a : b; }
-
-// fixed-order sum of red[0 .. 255] (one value per thread); every thread gets the total
-__device__ __forceinline__ double gmm_block_sum(double* red, double v) {
-    const int tid = threadIdx.x;
-    __syncthreads();                                            // (red may still be read from the previous call)
-    red[tid] = v;
-    for (int o = 128; o > 0; o >>= 1) {
-        __syncthreads();
-        if (tid < o) red[tid] += red[tid + o];
-    }
-    __syncthreads();
-    return red[0];
-}
 
 // ---- Cholesky -------------------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(64) potrf_info_zero_kernel(int* info, int count) {
@@ -116,18 +105,10 @@ __global__ void __launch_bounds__(256) potrf_syrk_kernel(double* A, int lda, lon
     f64x4_t acc[2][2];
     fid_acc_zero(acc);
     fid_tile_abt(s, l21, lda, t0 + bi * FID_T, d, l21, lda, t0 + bj * FID_T, d, 0, GMM_NB, acc);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wr = wave >> 1, wc = wave & 1;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int col = t0 + bj * FID_T + wc * 32 + j * 16 + (lane & 15);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int row = t0 + bi * FID_T + wr * 32 + i * 16 + (lane >> 4) + 4 * r;
-                if (row < d && col <= row) base[(size_t)row * lda + col] -= acc[i][j][r];
-            }
-        }
+    fid_tile_each(acc, [&](int r, int c, double v) {
+        const int row = t0 + bi * FID_T + r, col = t0 + bj * FID_T + c;
+        if (row < d && col <= row) base[(size_t)row * lda + col] -= v;
+    });
 }
 
 extern "C" int cdf_potrf_f64(double* a, int lda, long long stride, int d, int count, int* info, void* stream) {
@@ -187,21 +168,16 @@ __global__ void __launch_bounds__(256) trtri_offdiag_kernel(const double* L, int
     const int i0 = bi * FID_T, j0 = bj * FID_T;
     const double* l = L + (size_t)k * stride_l;
     double* pt = PT + (size_t)k * stride_p;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wr = wave >> 1, wc = wave & 1;
-    const int c16 = lane & 15, kq = lane >> 4;
     f64x4_t acc[2][2];
     fid_acc_zero(acc);
     fid_tile_abt(s, l, ldl, i0, d, pt, ldp, j0, d, j0, i0, acc);
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) s[(wr * 32 + i * 16 + kq + 4 * r) * FID_P + wc * 32 + j * 16 + c16] = acc[i][j][r];
+    fid_tile_each(acc, [&](int r, int c, double v) { s[r * FID_P + c] = v; });
     __syncthreads();
     fid_acc_zero(acc);
     const double* pii = pt + (size_t)i0 * ldp + i0;
     const int nb = gmm_min(FID_T, d - i0);
+    // the second product keeps a loop of its own: P[bi][bi] comes from global memory, not through the shared loader's LDS buffers
+    const int wr = fid_wave_row(), wc = fid_wave_col(), c16 = threadIdx.x & 15, kq = (threadIdx.x & 63) >> 4;
     for (int ks = 0; ks < nb; ks += 4) {                        // (rows of W at or past nb are zero: L's rows past d were loaded as zeros)
         double a[2], b[2];
 #pragma unroll
@@ -215,20 +191,13 @@ __global__ void __launch_bounds__(256) trtri_offdiag_kernel(const double* L, int
 #pragma unroll
             for (int j = 0; j < 2; ++j) acc[i][j] = cdf_mfma_f64_16x16x4(a[i], b[j], acc[i][j]);
     }
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int col = j0 + wc * 32 + j * 16 + c16;        // (< i0 <= d)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int row = i0 + wr * 32 + i * 16 + kq + 4 * r;
-                if (row < d) {
-                    pt[(size_t)col * ldp + row] = -acc[i][j][r];
-                    pt[(size_t)row * ldp + col] = 0.0;
-                }
-            }
+    fid_tile_each(acc, [&](int r, int c, double v) {
+        const int row = i0 + r, col = j0 + c;                   // (col < i0 <= d)
+        if (row < d) {
+            pt[(size_t)col * ldp + row] = -v;
+            pt[(size_t)row * ldp + col] = 0.0;
         }
+    });
 }
 
 extern "C" int cdf_trtri_lower_f64(const double* l, int ldl, long long stride_l, double* pt, int ldp, long long stride_p, int d, int count,
@@ -283,7 +252,7 @@ __global__ void __launch_bounds__(256) logdet_diag_kernel(const double* M, int l
     const double* m = M + (size_t)blockIdx.x * stride;
     double v = 0.0;
     for (int j = threadIdx.x; j < d; j += 256) v += log(m[(size_t)j * ld + j]);
-    v = gmm_block_sum(red, v);
+    v = cdf_block_sum_f64(red, v);
     if (threadIdx.x == 0) out[blockIdx.x] = v;
 }
 
@@ -410,10 +379,10 @@ __global__ void __launch_bounds__(256) gmm_resp_kernel(const double* maha, int l
             r = hard ? (k == arg ? 1.0 : 0.0) : exp(gmm_lp(maha, ldm, logdet, logw, dlog2pi, k, row) - lse);
             resp[(size_t)k * ldr + row] = r;
         }
-        const double t = gmm_block_sum(red, r);
+        const double t = cdf_block_sum_f64(red, r);
         if (threadIdx.x == 0) partial[(size_t)blockIdx.x * (K + 1) + k] = t;
     }
-    const double t = gmm_block_sum(red, in ? lse : 0.0);
+    const double t = cdf_block_sum_f64(red, in ? lse : 0.0);
     if (threadIdx.x == 0) partial[(size_t)blockIdx.x * (K + 1) + K] = t;
 }
 
@@ -422,7 +391,7 @@ __global__ void __launch_bounds__(256) gmm_resp_fold_kernel(const double* partia
     const int k = blockIdx.x;
     double v = 0.0;
     for (int b = threadIdx.x; b < nblk; b += 256) v += partial[(size_t)b * (K + 1) + k];
-    v = gmm_block_sum(red, v);
+    v = cdf_block_sum_f64(red, v);
     if (threadIdx.x == 0) {
         if (k < K) nk[k] = v + 10.0 * DBL_EPSILON;
         else lse_sum[0] = v;

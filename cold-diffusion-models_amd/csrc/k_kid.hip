@@ -2,8 +2,9 @@
 // random subsets of two feature sets (torch-fidelity / clean-fid `kid`), all subsets in one launch pair.
 //
 // Per subset s the three Gram matrices Xs Xs^T, Ys Ys^T, Xs Ys^T (Xs = rows ix[s][0..m) of x, Ys = rows iy[s][0..m) of y) are walked in
-// 64 x 64 tiles on v_mfma_f64_16x16x4_f64, the tile form of k_fid.hip (cdf_f64_tile.h) with the operand rows fetched through the index
-// arrays.  A Gram matrix never goes to memory: the epilogue cubes the 16 accumulators of each lane, masks and sums them.
+// 64 x 64 tiles on v_mfma_f64_16x16x4_f64, the tile form of cdf_f64_tile.h: its X Y^T loader with the operand rows fetched through the index
+// arrays, its accumulator walk for the epilogue; the block sum is cdf_common.h's.  A Gram matrix never goes to memory: the epilogue cubes
+// the 16 accumulators of each lane, masks and sums them.
 //   * rows / columns at or past m are masked IN THE EPILOGUE: a padded row has Gram value 0, hence kernel value coef0^3, not 0;
 //   * XX and YY leave out position i == j (positions, not row numbers: a source row named twice counts off the diagonal);
 //   * XX and YY are symmetric: only tiles with bj >= bi are computed, an off-diagonal tile counts twice (an exact doubling); the blocks
@@ -16,19 +17,6 @@
 #include "colddiff.h"
 
 #define KID_MAX_T 46340     // T^2 tiles is grid.x: T^2 <= 2^31 - 1
-
-// the sum of v over the block's 256 threads, the same tree whatever the values; red = 256 doubles of LDS nobody else is reading
-__device__ __forceinline__ double kid_block_sum(double* red, double v) {
-    const int tid = threadIdx.x;
-    __syncthreads();                                            // (red may still be read from the previous call)
-    red[tid] = v;
-    for (int o = 128; o > 0; o >>= 1) {
-        __syncthreads();
-        if (tid < o) red[tid] += red[tid + o];
-    }
-    __syncthreads();
-    return red[0];
-}
 
 // grid (T T, 3, nsub), T = ceil(m / 64): block x = tile bi T + bj, y = pair (0: XX, 1: YY, 2: XY), z = subset.
 __global__ void __launch_bounds__(256) kid_poly3_kernel(const double* X, int ldx, const int* IX, const double* Y, int ldy, const int* IY, int m,
@@ -50,22 +38,14 @@ __global__ void __launch_bounds__(256) kid_poly3_kernel(const double* X, int ldx
     f64x4_t acc[2][2];
     fid_acc_zero(acc);
     fid_tile_abt_indexed(s, A, lda, ia, bi * FID_T, m, B, ldb, ib, bj * FID_T, m, d, acc);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wr = wave >> 1, wc = wave & 1;
     double v = 0.0;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int col = bj * FID_T + wc * 32 + j * 16 + (lane & 15);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int row = bi * FID_T + wr * 32 + i * 16 + (lane >> 4) + 4 * r;
-                const double z = gamma * acc[i][j][r] + coef0;
-                const double k3 = z * z * z;
-                v += row < m && col < m && !(sym && row == col) ? k3 : 0.0;
-            }
-        }
-    v = kid_block_sum(s, v);                                    // (every wave is past its reads of s: fid_tile_abt_indexed's last barrier)
+    fid_tile_each(acc, [&](int r, int c, double g) {           // (the walk's order is the lane's order of summation)
+        const int row = bi * FID_T + r, col = bj * FID_T + c;
+        const double z = gamma * g + coef0;
+        const double k3 = z * z * z;
+        v += row < m && col < m && !(sym && row == col) ? k3 : 0.0;
+    });
+    v = cdf_block_sum_f64(s, v);                                // (every wave is past its reads of s: fid_k_loop's last barrier)
     if (threadIdx.x == 0) *dst = sym && bi < bj ? 2.0 * v : v;
 }
 
@@ -78,7 +58,7 @@ __global__ void __launch_bounds__(256) kid_fold_kernel(const double* partial, lo
         const double* src = partial + ((size_t)sub * 3 + p) * tiles;
         double v = 0.0;
         for (long long t = threadIdx.x; t < tiles; t += 256) v += src[t];
-        sum[p] = kid_block_sum(red, v);
+        sum[p] = cdf_block_sum_f64(red, v);
     }
     if (threadIdx.x == 0) {
         const double mm = (double)m;

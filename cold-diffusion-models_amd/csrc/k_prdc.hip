@@ -1,5 +1,5 @@
 // k_prdc.hip — the two k-NN passes behind improved precision / recall (Kynkaanniemi et al. 2019, torch-fidelity's `prc`) and density /
-// coverage (Naeem et al. 2020) of two fp64 feature sets, on v_mfma_f64_16x16x4_f64 (the tile form of cdf_f64_tile.h).
+// coverage (Naeem et al. 2020) of two fp64 feature sets, on v_mfma_f64_16x16x4_f64 (the tile form of cdf_f64_tile.h: its X Y^T loader and its accumulator map).
 //
 // Definitions (include/colddiff.h holds the same text; colddiff/metrics.py prdc_device builds the four numbers from them).  X: n rows,
 // Y: m rows, d features, neighbourhood size k.  Every comparison is on SQUARED Euclidean distances in fp64, no square root is taken:
@@ -38,15 +38,8 @@ static inline int prdc_per_split(int rt, int ct) {
 }
 static inline int prdc_splits(int rt, int ct) { return cdf_cdiv(ct, prdc_per_split(rt, ct)); }
 
-// D of the lane's accumulator (i, j, r): row bi 64 + prdc_row(i, r), column bj 64 + prdc_col(j) of the tile
-__device__ __forceinline__ int prdc_row(int i, int r) {
-    const int lane = threadIdx.x & 63, wr = threadIdx.x >> 7;
-    return wr * 32 + i * 16 + (lane >> 4) + 4 * r;
-}
-__device__ __forceinline__ int prdc_col(int j) {
-    const int lane = threadIdx.x & 63, wc = (threadIdx.x >> 6) & 1;
-    return wc * 32 + j * 16 + (lane & 15);
-}
+// D of the lane's accumulator (i, j, r) is row bi 64 + fid_tile_row(i, r), column bj 64 + fid_tile_col(j); both kernels walk j outermost, with
+// what belongs to a column (its norm, its radius) loaded once per j
 __device__ __forceinline__ double prdc_dist(double na, double nb, double ab) { return fmax(0.0, (na + nb) - 2.0 * ab); }
 
 // v into the ascending list (the largest element drops out); no branch, no index: the list stays in registers
@@ -75,7 +68,7 @@ __global__ void __launch_bounds__(256) knn_sq_kernel(const double* X, int ldx, i
     for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            const int row = bi * FID_T + prdc_row(i, r);
+            const int row = bi * FID_T + fid_tile_row(i, r);
             rn[i][r] = row < n ? norms[row] : 0.0;
         }
     double list[KL];
@@ -87,14 +80,14 @@ __global__ void __launch_bounds__(256) knn_sq_kernel(const double* X, int ldx, i
         fid_tile_abt(s, X, ldx, bi * FID_T, n, X, ldx, bj * FID_T, n, 0, d, acc);
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-            const int col = bj * FID_T + prdc_col(j);
+            const int col = bj * FID_T + fid_tile_col(j);
             const double cn = col < n ? norms[col] : 0.0;
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    const int row = bi * FID_T + prdc_row(i, r);
-                    s[prdc_row(i, r) * PRDC_DP + prdc_col(j)] = col < n && col != row ? prdc_dist(rn[i][r], cn, acc[i][j][r]) : INFINITY;
+                    const int row = bi * FID_T + fid_tile_row(i, r);
+                    s[fid_tile_row(i, r) * PRDC_DP + fid_tile_col(j)] = col < n && col != row ? prdc_dist(rn[i][r], cn, acc[i][j][r]) : INFINITY;
                 }
         }
         __syncthreads();
@@ -154,7 +147,7 @@ __global__ void __launch_bounds__(256) ball_counts_kernel(const double* A, int l
     for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            const int row = bi * FID_T + prdc_row(i, r);
+            const int row = bi * FID_T + fid_tile_row(i, r);
             rn[i][r] = row < na ? anorm[row] : 0.0;
             rr[i][r] = rrow && row < na ? rrow[row] : -1.0;     // (D >= 0: a radius of -1 counts nothing)
             ccol[i][r] = crow[i][r] = 0;
@@ -165,7 +158,7 @@ __global__ void __launch_bounds__(256) ball_counts_kernel(const double* A, int l
         fid_tile_abt(s, A, lda, bi * FID_T, na, B, ldb, bj * FID_T, nb, 0, d, acc);
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-            const int col = bj * FID_T + prdc_col(j);
+            const int col = bj * FID_T + fid_tile_col(j);
             const bool in = col < nb;
             const double cn = in ? bnorm[col] : 0.0;
             const double rc = rcol && in ? rcol[col] : -1.0;
@@ -182,13 +175,13 @@ __global__ void __launch_bounds__(256) ball_counts_kernel(const double* A, int l
     // cnt[row][32 lanes of that row][2] as ints in the operand LDS (every wave is past its reads of s: fid_tile_abt's last barrier; a
     // block without a tile has not touched s)
     int* cnt = (int*)s;
-    const int lane = threadIdx.x & 63, wc = (threadIdx.x >> 6) & 1, slot = wc * 16 + (lane & 15);
+    const int slot = fid_wave_col() * 16 + (threadIdx.x & 15);
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            cnt[(prdc_row(i, r) * 32 + slot) * 2 + 0] = ccol[i][r];
-            cnt[(prdc_row(i, r) * 32 + slot) * 2 + 1] = crow[i][r];
+            cnt[(fid_tile_row(i, r) * 32 + slot) * 2 + 0] = ccol[i][r];
+            cnt[(fid_tile_row(i, r) * 32 + slot) * 2 + 1] = crow[i][r];
         }
     __syncthreads();
     const int tid = threadIdx.x;

@@ -261,6 +261,11 @@ def test_fid_kernels_use_no_scratch_and_the_f64_mfma():
                         "-S", os.path.join(csrc, "k_fid.hip"), "-o", "-", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage"],
                        capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-2000:]
+    names = re.findall(r"Function Name: (\S+)", r.stderr)
     sizes = [int(v) for v in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", r.stderr)]
-    assert len(sizes) == 2 and sizes == [0, 0], r.stderr[-2000:]
-    assert r.stdout.count("v_mfma_f64_16x16x4_f64") >= 32                          # 16 per K chunk in each kernel
+    # the two matrix-core kernels and the merge of two accumulators, which has no MFMA
+    assert len(names) == 3 and all(sum(k in n for n in names) == 1 for k in ("gemm_f64_kernel", "moments_f64_kernel", "moments_merge_f64_kernel"))
+    assert sizes == [0] * 3, r.stderr[-2000:]
+    bodies = re.split(r"^\s*\.globl\s+", r.stdout, flags=re.M)[1:]
+    main = [b for b in bodies if "gemm_f64_kernel" in b.split(None, 1)[0] or "moments_f64_kernel" in b.split(None, 1)[0]]
+    assert len(main) == 2 and all(b.count("v_mfma_f64_16x16x4_f64") >= 16 for b in main)      # 16 per K chunk, in each of the two

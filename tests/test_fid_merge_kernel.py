@@ -1,4 +1,4 @@
-"""`cdf_moments_merge_f64` (csrc/k_fid_merge.hip): accumulator b of `cdf_moments_f64`, re-centred on a's pivot, added to accumulator a.
+"""`cdf_moments_merge_f64` (csrc/k_fid.hip): accumulator b of `cdf_moments_f64`, re-centred on a's pivot, added to accumulator a.
 Simulator and MI355X.
 
 Exact tests: the rows are integers in [-8, 8] and both pivots are means of a power-of-two number of rows (<= 8), so every centred value,

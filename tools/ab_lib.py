@@ -27,7 +27,7 @@ def main():
         open(os.path.join(hdr_dir, os.path.basename(path)), "w").write(show(path))
     flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wno-unused-result", "-I", hdr_dir]
     objs = []
-    for f in sorted(x for x in os.listdir(CSRC) if x.endswith(".hip")):
+    for f in sorted({x for x in os.listdir(CSRC) if x.endswith(".hip")} | set(names)):    # (a named source may exist in <rev> only)
         if f in names:
             src = os.path.join(out_dir, f)
             open(src, "w").write(show(f"cold-diffusion-models_amd/csrc/{f}"))
