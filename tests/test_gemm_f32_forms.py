@@ -56,7 +56,7 @@ from colddiff import convdesc as cd
 from poison import nan_empty
 from test_kernels import P, r4
 from test_kernels_production import K_SUM, U, check, sum_bound, twice
-from test_gemm_production import _conv64, _dist, _epilogue64, _nchw, _wgrad_ref64, gemm_plan, wgrad_plan
+from test_gemm_production import _conv64, _dist, _epilogue64, _khw, _nchw, _wgrad_ref64, gemm_plan, tap_mask, wgrad_plan
 
 BIG = 1.0e30                                                 # the finite value of in-quad pad channels (include/colddiff.h: cdf_conv_gemm)
 NAN32 = torch.tensor(float("nan")).view(torch.int32).item()  # the poison bit patterns of tests/poison.py
@@ -203,17 +203,20 @@ def _max_taps(pl):
 
 def _igemm_case(be, r):
     pl = gemm_plan(r.kind, r.H, r.W, r.k, r.s, r.pad)
-    B, Cin, Cout, k, KK = r.B, r.Cin, r.Cout, r.k, r.k * r.k
+    B, Cin, Cout, k = r.B, r.Cin, r.Cout, r.k
+    kh, kw = _khw(k)                                         # (k: an int, a (kh, kw) pair or a TapSubset -- test_gemm_production.gemm_plan)
+    KK = kh * kw
     ldx, ldo, ldh = r.xld or r4(Cin), r4(Cout), r4(Cout) + 8
     ldy = r.yld or ldo
     tag = "igemm " + "-".join(map(str, r[:20]))
-    g = torch.Generator().manual_seed(Cin * 131 + Cout * 7 + k + r.H)
+    g = torch.Generator().manual_seed(Cin * 131 + Cout * 7 + kh + r.H)
     rn = lambda *s_: torch.randn(*s_, generator=g)
     x = rn(B, pl.H, pl.W, Cin)
     gather = r.kind in ("conv_fwd", "convT_dgrad")
-    w = rn(*((Cout, Cin, k, k) if gather else (Cin, Cout, k, k))) / math.sqrt(Cin * KK)
+    w = rn(*((Cout, Cin, kh, kw) if gather else (Cin, Cout, kh, kw))) / math.sqrt(Cin * KK)
     wp = torch.zeros(KK, Cin, ldo)                           # [tap][Cin][ldw], pad columns zero (cdf_pack_weight's contract)
     wp[..., :Cout] = (w.permute(2, 3, 1, 0) if gather else w.permute(2, 3, 0, 1)).reshape(KK, Cin, Cout)
+    w = tap_mask(w, k)                                       # (a tap subset: every tap is packed, the reference has the absent ones zeroed)
     osh = (B, pl.OH, pl.OW)
     t, o32, ad = {}, {}, {}
     t["x"], t["w"] = be.to(_padded(x, ldx, r.xoff, BIG)), be.to(wp)

@@ -33,6 +33,7 @@ K_SUM stays 4 for the GEMMs.  Worst error / bound over all cases of this module 
 """
 import ctypes
 import math
+from typing import NamedTuple
 
 import pytest
 import torch
@@ -56,15 +57,54 @@ def decode(code):
 
 
 def _pads(pad):
-    """pad >= 0: symmetric; -1: one row / column at the bottom / right only (the strided 3 x 3 downsampling convolution of config 2)."""
+    """(top, left, bottom, right).  pad >= 0: symmetric; -1: one row / column at the bottom / right only (the strided 3 x 3 downsampling
+    convolution of config 2); a pair (ph, pw): ph rows above and below, pw columns left and right (the 1 x 7 / 7 x 1 layers of the FID
+    extractor)."""
+    if isinstance(pad, tuple):
+        return (pad[0], pad[1], pad[0], pad[1])
     return (0, 0, 1, 1) if pad == -1 else (pad, pad, pad, pad)
 
 
+class TapSubset(NamedTuple):
+    """The `k` of a row that launches taps lo .. hi-1 (row-major, tap = ky kw + kx) of a kh x kw convolution over the weight packed with
+    all kh kw taps -- the plans colddiff.inception._tap_parts cuts a 25-tap layer into (0 .. 15, then 16 .. 24, accumulating).  Such a row
+    computes the convolution whose absent taps have zero weights."""
+    kh: int
+    kw: int
+    lo: int
+    hi: int
+
+    def __str__(self):
+        return f"{self.kh}x{self.kw}taps{self.lo}to{self.hi}"
+
+
+def _khw(k):
+    """(kh, kw) of a row's k: an int (square), a pair, or a TapSubset."""
+    return (k, k) if isinstance(k, int) else (k[0], k[1])
+
+
+def tap_mask(w, k):
+    """w [.][.][kh][kw] with the taps a TapSubset row does not launch set to zero (any other k: w itself)."""
+    if not isinstance(k, TapSubset):
+        return w
+    keep = torch.zeros(k.kh * k.kw, dtype=torch.bool)
+    keep[k.lo:k.hi] = True
+    return w * keep.view(k.kh, k.kw).to(w.device, w.dtype)
+
+
 def gemm_plan(kind, H, W, k, s, pad):
-    """H, W: the arguments of the colddiff.convdesc constructor `kind` (the convolution's own input size)."""
+    """H, W: the arguments of the colddiff.convdesc constructor `kind` (the convolution's own input size).  k, pad: an int or an (h, w)
+    pair; k a TapSubset (conv_fwd only): the full plan's geometry with that slice of its taps, weight indices unchanged."""
+    kh, kw = _khw(k)
+    if isinstance(k, TapSubset):
+        assert kind == "conv_fwd"
+        full = cd.conv_fwd(H, W, kh, kw, s, *_pads(pad))
+        d = list(full.desc)
+        taps = [tuple(d[3 + 3 * t:6 + 3 * t]) for t in range(d[2])][k.lo:k.hi]
+        return cd.GemmPlan(full.H, full.W, full.OH, full.OW, full.QH, full.QW, full.os, full.istride, [(0, 0, taps)], full.ntaps_w)
     if kind in ("conv_fwd", "conv_dgrad"):
-        return getattr(cd, kind)(H, W, k, k, s, *_pads(pad))
-    return getattr(cd, kind)(H, W, k, k, s, pad)
+        return getattr(cd, kind)(H, W, kh, kw, s, *_pads(pad))
+    return getattr(cd, kind)(H, W, kh, kw, s, pad)
 
 
 def wgrad_plan(kind, H, W, k, s, pad):
@@ -279,7 +319,8 @@ def _wide(plane, C):
 
 def _conv64(kind, x, w, k, s, pad, out_hw):
     """The convolution behind a `kind` plan in float64: x NCHW, w in the orientation _weights makes ([out][in][k][k] for the gathering
-    kinds conv_fwd / convT_dgrad, [in][out][k][k] for the scattering kinds conv_dgrad / convT_fwd)."""
+    kinds conv_fwd / convT_dgrad, [in][out][k][k] for the scattering kinds conv_dgrad / convT_fwd).  The kernel size is w's own, so a
+    rectangular w and a pad pair (_pads) need nothing more; a TapSubset row passes w with its absent taps zeroed (tap_mask)."""
     pt, pl, pb, pr = _pads(pad)
     if kind in ("conv_fwd", "convT_dgrad"):
         return F.conv2d(F.pad(x, (pl, pr, pt, pb)), w, stride=s)
@@ -345,11 +386,14 @@ def _nchw(t, C):
 
 def _weights(be, kind, Cin, Cout, k, ns, seed):
     """A weight in the orientation its convolution kind stores it, packed by cdf_pack_weight_bf16 the way the product packs it for this
-    GEMM; returns (fp32 weight, hi plane, lo plane or None, ldk, the float64 weights the planes hold: hi, lo)."""
-    KK = k * k
+    GEMM; returns (fp32 weight, hi plane, lo plane or None, ldk, the float64 weights the planes hold: hi, lo).  k: an int, a (kh, kw) pair or
+    a TapSubset -- then every tap is packed, as the product packs it, and the three returned weights have the absent taps zeroed: they
+    are the reference's operands, the planes are the kernel's."""
+    kh, kw = _khw(k)
+    KK = kh * kw
     g = torch.Generator().manual_seed(seed)
     gather = kind in ("conv_fwd", "convT_dgrad")
-    w = torch.randn((Cout, Cin, k, k) if gather else (Cin, Cout, k, k), generator=g) / math.sqrt(Cin * KK)
+    w = torch.randn((Cout, Cin, kh, kw) if gather else (Cin, Cout, kh, kw), generator=g) / math.sqrt(Cin * KK)
     ldk = (Cin + 31) // 32 * 32
     hi = nan_empty(be, KK, Cout, ldk, dtype=torch.int16)
     lo = nan_empty(be, KK, Cout, ldk, dtype=torch.int16) if ns == 3 else None
@@ -360,7 +404,7 @@ def _weights(be, kind, Cin, Cout, k, ns, seed):
     def unpack(plane):                                       # [tap][N][K] -> the weight's own layout
         t = _wide(plane, Cin)
         return (t.permute(1, 2, 0) if gather else t.permute(2, 1, 0)).reshape(w.shape).contiguous()
-    return w, hi, lo, ldk, unpack(hi), (unpack(lo) if ns == 3 else None)
+    return tap_mask(w, k), hi, lo, ldk, tap_mask(unpack(hi), k), (tap_mask(unpack(lo), k) if ns == 3 else None)
 
 
 def _ref_chunks(B, per_image_bytes):

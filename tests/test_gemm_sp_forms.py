@@ -62,7 +62,7 @@ import torch
 from poison import nan_empty
 from test_kernels import P, r4
 from test_kernels_production import K_SUM, U, check, sum_bound, twice
-from test_gemm_production import _conv64, _dist, _epilogue64, _nchw, _weights, _wgrad_ref64, gemm_plan, wgrad_plan
+from test_gemm_production import _conv64, _dist, _epilogue64, _khw, _nchw, _weights, _wgrad_ref64, gemm_plan, wgrad_plan
 
 BIG = 1.0e30                                                 # the finite value of in-quad pad channels (include/colddiff.h: cdf_conv_gemm)
 NAN32 = torch.tensor(float("nan")).view(torch.int32).item()  # the poison bit pattern of tests/poison.py
@@ -212,14 +212,17 @@ def gs_args(r, ad=None, stream=0):
             ldo if has("m") else 0, r.act, r.mm, r.acc, r.split, stream)
 
 
-def _sp_gemm_case(be, r):
+def _sp_gemm_case(be, r, split_margin=None):
+    """r.k, r.pad: an int, an (h, w) pair, or (k) a TapSubset (test_gemm_production.gemm_plan).  split_margin: when given, the float64
+    sum of the split operands alone must lie within that fraction of the second assertion's tolerance of the true convolution -- a row
+    that misses it has inputs the operand split cannot carry, whatever the kernel does."""
     pl = gemm_plan(r.kind, r.H, r.W, r.k, r.s, r.pad)
     B, Cin, Cout, k, ns = r.B, r.Cin, r.Cout, r.k, r.split
     ldx, ldo = r.xld or r4(Cin), r4(Cout)
     ldy, ldr, ldp = r.yld or ldo, r.ldr or ldo, r.ldp or ldo
     assert r.xoff % 4 == 0 and r.yoff % 4 == 0 and r.xoff + r4(Cin) <= ldx and r.yoff + Cout <= ldy and ldr >= Cout and ldp >= Cout
     tag = "sp gemm " + "-".join(map(str, r))
-    g = torch.Generator().manual_seed(Cin * 131 + Cout * 7 + k + r.H)
+    g = torch.Generator().manual_seed(Cin * 131 + Cout * 7 + _khw(k)[0] + r.H)
     rn = lambda *s_: torch.randn(*s_, generator=g)
     x = rn(B, pl.H, pl.W, Cin)
     w, whi, wlo, ldk, wh64, wl64 = _weights(be, r.kind, Cin, Cout, k, ns, Cin * 7 + Cout)
@@ -277,6 +280,8 @@ def _sp_gemm_case(be, r):
         check(f"{tag} pre", _nchw(got["pre"], Cout), prer, e_pre)
         assert _poison_outside(got["pre"], 0, Cout), (tag, "pre: a pad column changed")
     tol = (3e-5 if ns == 3 else 2e-2) * max(1.0, yt.abs().max().item())
+    if split_margin is not None:
+        check(f"{tag} split operands alone against the true float64 convolution", yr, yt, split_margin * tol)
     check(f"{tag} true float64 convolution (split {ns})", gy, yt, tol)
     return form
 

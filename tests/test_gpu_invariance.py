@@ -268,6 +268,11 @@ for _names, _test in ((("cdf_dwconv7", "cdf_dwconv7_io", "cdf_dwconv7_planes"), 
                       (("cdf_groupnorm_bwd_ex", "cdf_groupnorm_nchunk"), "test_groupnorm_bwd_forms")):
     for _name in _names:
         COVERED_AT_PRODUCTION_SHAPE[_name].append(_ND + _test)
+# the FID extractor's launches of the two conv GEMM entry points, at the extractor's own shapes (test_coverage_guard holds a recording of
+# the extractor against that module's form tables)
+_IF = "test_inception_forms.py::"
+COVERED_AT_PRODUCTION_SHAPE["cdf_conv_gemm_bf16"] += [_IF + "test_extractor_sp_forms", _IF + "test_extractor_sp_production_shapes"]
+COVERED_AT_PRODUCTION_SHAPE["cdf_conv_gemm"] += [_IF + "test_extractor_f32_forms", _IF + "test_extractor_f32_production_shapes"]
 # entry points with nothing shape-dependent to test at scale, with the reason
 EXEMPT = {
     "cdf_last_error": "host-side error string",
@@ -357,7 +362,9 @@ def test_coverage_guard(bench_data):
     cdf_conv_wgrad) likewise: every form (test_gemm_f32_forms.f32_gemm_form / f32_wgrad_form of the recorded arguments) must be one a row
     of that module's case tables has, and the forms it flags as reached must still be reached.  The in-kernel-split pair
     (cdf_conv_gemm_bf16, cdf_conv_wgrad_bf16) the same way against test_gemm_sp_forms (sp_gemm_form / sp_wgrad_form).  The depthwise,
-    LayerNorm and GroupNorm entry points (_NORM_DW) the same way against the six classifiers and case tables of test_norm_dw_forms."""
+    LayerNorm and GroupNorm entry points (_NORM_DW) the same way against the six classifiers and case tables of test_norm_dw_forms.
+    The FID extractor is a recording of its own (test_inception_forms.extractor_calls: none of the four runs above launches it): the forms
+    of its cdf_conv_gemm_bf16 / cdf_conv_gemm calls the same way against test_inception_forms' tables (check_recording)."""
     import os
     import re
     from test_kernels_production import BENCH_UNPACK
@@ -447,3 +454,7 @@ def test_coverage_guard(bench_data):
         assert not untested, "%s forms the product reaches without a test_norm_dw_forms row: %s" % (what, untested)
         stale = sorted(flagged - set(reached), key=repr)
         assert not stale, "test_norm_dw_forms flags %s forms as reached that the recordings no longer contain: %s" % (what, stale)
+    # ---- the FID extractor's conv GEMM launches (colddiff/inception.py), form by form: one forward on 64 x 64 images at B = 50 and B = 1 in
+    # the default mode, in bf16 and in f32 -- every recorded form must have a row in test_inception_forms, every form it flags is recorded
+    import test_inception_forms as tif
+    tif.check_recording(tif.extractor_calls(DEV))

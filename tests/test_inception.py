@@ -53,39 +53,60 @@ def _nhwc(x):
     return x.permute(0, 2, 3, 1).contiguous()
 
 
-def _check_block(mine, ref, x, tol=2e-4):
+def _check_block(mine, ref, x, tol=2e-4, dev="cpu"):
     mine.load_state_dict(ref.state_dict())
+    mine = mine.to(dev)
     with torch.no_grad():
         want = ref(x)
-        got = mine.run(_nhwc(x)).permute(0, 3, 1, 2)
+        got = mine.run(_nhwc(x).to(dev)).cpu().permute(0, 3, 1, 2)
     assert got.shape == want.shape
     err = (got - want).abs().max().item() / max(1.0, want.abs().max().item())
+    print(type(mine).__name__, tuple(x.shape), "rel err", err)
     assert err <= tol, err
     return err
 
 
-def test_inception_blocks_on_the_simulator(emu):
-    """Stem layers (stride 2 without padding, 1x1, padded 3x3 on a 3-channel image) and the A / B / C / D blocks (5x5, 1x7 / 7x1
-    convs, stride-2 reductions, both pool flavours, concat-free branch outputs) against the restatement, small spatial sizes."""
+def _blocks_case(dev, wide):
+    """Stem layers (stride 2 without padding, 1x1, padded 3x3 on a 3-channel image) and the A / B / C / D / E blocks (5x5, 1x7 / 7x1
+    convs, stride-2 reductions, both pool flavours, concat-free branch outputs) against the restatement (oracle/inception_ref.py).
+    wide = 0: B = 1 on 3x3 to 5x5 maps;  wide = 1: B = 2 on non-square maps -- 9 x 10 for the C and D blocks, so that a 7-tap row has all
+    seven taps inside the image for some pixels and M = 180 has a second 128-row tile."""
     from colddiff import inception as I
     torch.manual_seed(1)
     ref = R.randomise(R.FidInception3(), seed=3)
-    x = torch.rand(1, 3, 15, 15) * 2 - 1
-    x4 = torch.zeros(1, 15, 15, 4)
+    blocks = ((lambda: I.FIDInceptionA(192, 32), ref.Mixed_5b, 192, (5, 5), (5, 6)), (lambda: I.InceptionB(288), ref.Mixed_6a, 288, (5, 5), (7, 9)),
+              (lambda: I.FIDInceptionC(768, 128), ref.Mixed_6b, 768, (4, 4), (9, 10)), (lambda: I.InceptionD(768), ref.Mixed_7a, 768, (5, 5), (9, 10)),
+              (lambda: I.FIDInceptionE_1(1280), ref.Mixed_7b, 1280, (3, 3), (3, 4)), (lambda: I.FIDInceptionE_2(2048), ref.Mixed_7c, 2048, (3, 3), (3, 4)))
+    B, H, W = ((1, 15, 15), (2, 15, 17))[wide]
+    x = torch.rand(B, 3, H, W) * 2 - 1
+    x4 = torch.zeros(B, H, W, 4)
     x4[..., :3] = _nhwc(x)
     stem = [I.BasicConv2d(3, 32, 3, stride=2), I.BasicConv2d(32, 32, 3), I.BasicConv2d(32, 64, 3, padding=1)]
-    h, hr = x4, x
+    h, hr = x4.to(dev), x
     for m, r in zip(stem, (ref.Conv2d_1a_3x3, ref.Conv2d_2a_3x3, ref.Conv2d_2b_3x3)):
         m.load_state_dict(r.state_dict())
         with torch.no_grad():
-            h, hr = m.run(h), r(hr)
-        assert (h.permute(0, 3, 1, 2) - hr).abs().max() <= 2e-4 * max(1.0, hr.abs().max().item())
-    _check_block(I.FIDInceptionA(192, 32), ref.Mixed_5b, torch.randn(1, 192, 5, 5))
-    _check_block(I.InceptionB(288), ref.Mixed_6a, torch.randn(1, 288, 5, 5))
-    _check_block(I.FIDInceptionC(768, 128), ref.Mixed_6b, torch.randn(1, 768, 4, 4))
-    _check_block(I.InceptionD(768), ref.Mixed_7a, torch.randn(1, 768, 5, 5))
-    _check_block(I.FIDInceptionE_1(1280), ref.Mixed_7b, torch.randn(1, 1280, 3, 3))
-    _check_block(I.FIDInceptionE_2(2048), ref.Mixed_7c, torch.randn(1, 2048, 3, 3))
+            h, hr = m.to(dev).run(h), r(hr)
+        assert (h.cpu().permute(0, 3, 1, 2) - hr).abs().max() <= 2e-4 * max(1.0, hr.abs().max().item())
+    for make, r, C, *maps in blocks:
+        _check_block(make(), r, torch.randn(B, C, *maps[wide]), dev=dev)
+
+
+def test_inception_blocks_on_the_simulator(emu):
+    """The stem and every block at B = 1 on 3x3 to 5x5 maps (_blocks_case)."""
+    _blocks_case("cpu", 0)
+
+
+def test_inception_blocks_wide_on_the_simulator(emu):
+    """... and at B = 2 on non-square maps, 9 x 10 for the blocks with 7-tap rows."""
+    _blocks_case("cpu", 1)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("wide", [0, 1])
+def test_inception_blocks_on_the_gpu(wide):
+    """The same blocks, shapes and tolerance on the MI355X."""
+    _blocks_case("cuda:0", wide)
 
 
 def test_fid_state_dict_layouts(emu):
