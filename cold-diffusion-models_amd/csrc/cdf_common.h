@@ -126,6 +126,46 @@ __device__ __forceinline__ void cdf_acc_stage(float* tile, int pitch, int row0, 
     for (int i = 0; i < MT; ++i) cdf_acc_stage(tile, pitch, row0 + i * 32, col0, acc[i], half, l31);
 }
 
+// ---- the same 32 x 32 block as 2 x 2 accumulators of the 16 x 16 x 32 bf16 MFMA (f32x4q_t) ------------------------------------
+// q[a][b] is the 16 x 16 sub-block at rows 16 a, columns 16 b.  Lane l holds column l & 15 of each; its register r is row
+// cdf_acc_row16(r, l >> 4).  16 accumulator registers per lane, as f32x16_t has, and the staged [row][col] tile is the same tile.
+struct f32x4q_t {
+    f32x4_t q[2][2];
+};
+constexpr int cdf_acc_row16(int r, int quarter) { return 4 * quarter + r; }
+__device__ __forceinline__ void cdf_acc_zero(f32x4q_t& acc) {
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) acc.q[a][b][r] = 0.f;
+}
+template <int MT, int NT>
+__device__ __forceinline__ void cdf_acc_zero(f32x4q_t (&acc)[MT][NT]) {
+#pragma unroll
+    for (int i = 0; i < MT; ++i)
+#pragma unroll
+        for (int j = 0; j < NT; ++j) cdf_acc_zero(acc[i][j]);
+}
+// same arguments as the f32x16_t form (half = lane >> 5, l31 = lane & 31): the lane's quarter is 2 half + (l31 >> 4), its column l31 & 15
+__device__ __forceinline__ void cdf_acc_stage(float* tile, int pitch, int row0, int col0, const f32x4q_t& acc, int half, int l31) {
+    const int quarter = 2 * half + (l31 >> 4), l15 = l31 & 15;
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) tile[(row0 + 16 * a + cdf_acc_row16(r, quarter)) * pitch + col0 + 16 * b + l15] = acc.q[a][b][r];
+}
+template <int MT, int NT>
+__device__ __forceinline__ void cdf_acc_stage(float* tile, int pitch, int row0, int col0, const f32x4q_t (&acc)[MT][NT], int half, int l31) {
+#pragma unroll
+    for (int i = 0; i < MT; ++i)
+#pragma unroll
+        for (int j = 0; j < NT; ++j) cdf_acc_stage(tile, pitch, row0 + i * 32, col0 + j * 32, acc[i][j], half, l31);
+}
+
 // 256 zero bytes: out-of-range operand elements are loaded from here, so that loads never sit behind a branch.
 // (one copy per translation unit; the contents never change)
 #ifdef CDF_EMU

@@ -16,13 +16,37 @@
 typedef short bf16x8_v __attribute__((ext_vector_type(8)));
 typedef short bf16x4_v __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4_v __attribute__((ext_vector_type(4)));
+// The two bf16 MFMA shapes.  CDF_MFMA_BF16: v_mfma_f32_32x32x16_bf16 (lane l: A[row l & 31][k = 8 (l >> 5) + j], B[k][col l & 31], j < 8;
+// C: cdf_acc_row, cdf_common.h).  CDF_MFMA16_BF16: v_mfma_f32_16x16x32_bf16 -- lane l holds A[row l & 15][k = 8 (l >> 4) + j] and
+// B[k = 8 (l >> 4) + j][col l & 15], j < 8; C register r of lane l is row 4 (l >> 4) + r, column l & 15 (cdf_acc_row16).  Same FLOPs per
+// cycle; a K loop that the chip's clock holds down can run faster on one than on the other (see cdf_halo_mfma, k_conv_halo.hip).
 #ifdef CDF_EMU
 #define CDF_MFMA_BF16(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0)
+// The simulator has no 16 x 16 x 32 product: restated here on its wave exchange (products summed in k order, like its 32 x 32 x 16 form).
+static inline f32x4_t cdf_emu_mfma_f32_16x16x32_bf16(bf16x8_v a, bf16x8_v b, f32x4_t c) {
+    const int w = hipemu::wave_id(), l = hipemu::lane_id();
+    for (int j = 0; j < 8; ++j) {
+        hipemu::g.wave_a[w][l * 8 + j] = emu_bf16_to_f32(a[j]);
+        hipemu::g.wave_b[w][l * 8 + j] = emu_bf16_to_f32(b[j]);
+    }
+    hipemu::wave_barrier();
+    for (int r = 0; r < 4; ++r) {
+        const int row = 4 * (l >> 4) + r, col = l & 15;
+        float acc = c[r];
+        for (int k = 0; k < 32; ++k) acc += hipemu::g.wave_a[w][((k >> 3) * 16 + row) * 8 + (k & 7)] * hipemu::g.wave_b[w][((k >> 3) * 16 + col) * 8 + (k & 7)];
+        c[r] = acc;
+    }
+    hipemu::wave_barrier();
+    return c;
+}
+#define CDF_MFMA16_BF16(a, b, c) cdf_emu_mfma_f32_16x16x32_bf16(a, b, c)
 static inline bf16x4_v cdf_lds_read_tr16(const unsigned short* p) { return hipemu::ds_read_tr16_b64(p); }
 #else
 typedef __bf16 bf16x8_hw __attribute__((ext_vector_type(8)));
 #define CDF_MFMA_BF16(a, b, c) \
     __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_hw, a), __builtin_bit_cast(bf16x8_hw, b), c, 0, 0, 0)
+#define CDF_MFMA16_BF16(a, b, c) \
+    __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_hw, a), __builtin_bit_cast(bf16x8_hw, b), c, 0, 0, 0)
 // ds_read_b64_tr_b16: the 16 lanes of a group pass the addresses of a [4 rows][16 cols] bf16 block (lane t: row t >> 2,
 // cols 4 (t & 3) .. +3, 8-byte aligned, any row pitch); lane t gets column t's 4 rows.
 __device__ __forceinline__ bf16x4_v cdf_lds_read_tr16(const unsigned short* p) {
@@ -46,8 +70,9 @@ constexpr int CDF_SP_CPITCH = 136;
 constexpr size_t CDF_SP_EPI_LDS = (size_t)128 * CDF_SP_CPITCH * sizeof(float);
 
 // BFF: the kernel's epilogue family (cdf_epilogue.h: ids 1..6 for fp32 tensors, 7..11 for bf16 activation storage = the NS == 1 kernels)
-template <int BM, int BN, int WM = 2, int WN = 2, bool BFF = false, class Args>
-__device__ __forceinline__ void cdf_sp_epilogue(const Args& a, const CdfPhase& ph, const f32x16_t (&acc)[BM / WM / 32][BN / WN / 32], float* cs,
+// (Acc: f32x16_t or f32x4q_t -- cdf_acc_stage writes the same staged tile from either)
+template <int BM, int BN, int WM = 2, int WN = 2, bool BFF = false, class Args, class Acc>
+__device__ __forceinline__ void cdf_sp_epilogue(const Args& a, const CdfPhase& ph, const Acc (&acc)[BM / WM / 32][BN / WN / 32], float* cs,
                                                 int tile_m, int tile_n, int M, int tid) {
     constexpr int CP = BN + 8, TM = BM / WM, TN = BN / WN, NTHR = 64 * WM * WN;
     const int lane = tid & 63, wave = tid >> 6, wm = wave / WN, wn = wave % WN, half = lane >> 5, l31 = lane & 31;
@@ -162,13 +187,54 @@ __device__ __forceinline__ void cdf_mma_tile(f32x16_t (&acc)[MT][NT], const bf16
     }
 }
 
+// The 16 x 16 x 32 form (f32x4q_t accumulators, same output tile per wave and same register counts): one MFMA spans the whole 32-deep K chunk,
+// so the first index of a fragment array is the 16-row half of the 32-row block instead of the k16 step -- ah[a][i] = rows 32 i + 16 a of
+// the wave's A tile, bh[b][j] = rows 32 j + 16 b of its B tile -- and a chunk is 4 MFMAs per 32 x 32 block and term instead of 2.  Term-major
+// like above; per accumulator the order is al*bh, ah*bl, ah*bh.
+template <int NS, int MT, int NT>
+__device__ __forceinline__ void cdf_mma_tile(f32x4q_t (&acc)[MT][NT], const bf16x8_v (&ah)[2][MT], const bf16x8_v (&al)[2][MT],
+                                             const bf16x8_v (&bh)[2][NT], const bf16x8_v (&bl)[2][NT]) {
+    auto term = [&](const bf16x8_v (&x)[2][MT], const bf16x8_v (&y)[2][NT]) {
+#pragma unroll
+        for (int i = 0; i < MT; ++i)
+#pragma unroll
+            for (int j = 0; j < NT; ++j)
+#pragma unroll
+                for (int a = 0; a < 2; ++a)
+#pragma unroll
+                    for (int b = 0; b < 2; ++b) acc[i][j].q[a][b] = CDF_MFMA16_BF16(x[a][i], y[b][j], acc[i][j].q[a][b]);
+    };
+    if constexpr (NS == 3) {
+        term(al, bh);
+        term(ah, bl);
+    }
+    term(ah, bh);
+}
+// the accumulator block of a K loop that runs on MFMA shape MF (32: 32 x 32 x 16, 16: 16 x 16 x 32)
+template <int MF> struct cdf_acc_of { typedef f32x16_t type; };
+template <> struct cdf_acc_of<16> { typedef f32x4q_t type; };
+
 // ---- what the K loops of the pre-split forward kernels (k_conv_spx / k_conv_halo / k_conv_rowhalo.hip) share --------------------------------
 // Operand planes in LDS are [rows][CDF_SP_RE bf16 = 64 B], filled by LDS-DMA in 16-row segments (one wave instruction each) and XOR-swizzled
-// on both sides: the 16-byte column c of row r lives at column c ^ ((r >> 2) & 3).
+// on both sides: the 16-byte column c of row r lives at column c ^ cdf_swz<MF>(r), by the MFMA shape MF of the kernel that reads it.
+//   MF = 32: (r >> 2) & 3.  A lane reads row r0 + (l & 31) at K block 2 ks + (l >> 5): each ds_read_b128 lane group is 16 rows of ONE K block,
+//     four per class r mod 4 with four distinct (r >> 2) & 3 -- all 64 banks once (k_conv_spx.hip).
+//   MF = 16: ((r >> 2) & 1) << 1.  A lane reads row r0 + (l & 15) at K block l >> 4.  ds_read_b128 serves the lanes in the groups {0-3, 12-15,
+//     20-27}, {4-11, 16-19, 28-31} and the same + 32: a group is rows r0 + {0-3, 12-15} at K block kb and rows r0 + {4-11} at kb ^ 1 (kb = 0,
+//     1, 2, 3 for the four groups).  Banks repeat every 256 B = 4 rows, so the 16 lanes are conflict-free iff, in each class r mod 4, the four
+//     rows of the group -- one from each quad of rows, T, T + 1, T + 2, T + 3 = r >> 2 -- land in four distinct 16-byte columns:
+//         f(T) ^ kb,  f(T + 3) ^ kb,  f(T + 1) ^ kb ^ 1,  f(T + 2) ^ kb ^ 1   all distinct, for every T (r0 is any row of a halo image).
+//     (r >> 2) & 3 gives T, T + 3, T, T + 3: 2-way.  Distinctness of f(T + 1), f(T + 2) and of f(T), f(T + 1) ^ 1 for every T says that
+//     consecutive quads differ in bit 1 of f; then f(T) and f(T + 2) ^ 1 share bit 1 and must agree in bit 0.  f(T) = (T & 1) << 1 is the
+//     simplest such map: the four columns are {0, 2, 3, 1} ^ kb (T even) or {2, 0, 1, 3} ^ kb (T odd).
 constexpr int CDF_SP_RE = 32;
-// this lane's DMA slot inside a segment: row lane >> 2, and the global 16-byte column (as an element offset) that lands in LDS column lane & 3
+template <int MF = 32>
+__device__ __forceinline__ int cdf_swz(int row) { return MF == 16 ? ((row >> 2) & 1) << 1 : (row >> 2) & 3; }
+// this lane's DMA slot inside a segment: row lane >> 2 (segments start at multiples of 16 rows: cdf_swz(row) = cdf_swz(lane >> 2)), and the
+// global 16-byte column (as an element offset) that lands in LDS column lane & 3
 __device__ __forceinline__ int cdf_dma_row(int lane) { return lane >> 2; }
-__device__ __forceinline__ int cdf_dma_col(int lane) { return ((lane & 3) ^ ((lane >> 4) & 3)) * 8; }
+template <int MF = 32>
+__device__ __forceinline__ int cdf_dma_col(int lane) { return ((lane & 3) ^ cdf_swz<MF>(lane >> 2)) * 8; }
 // weight row n of a tile, clamped into the matrix (rows past Cout fetch the last row again; the epilogue never stores them) ...
 __device__ __forceinline__ int cdf_w_row(int n, int Cout) { return n < Cout ? n : Cout - 1; }
 // ... and the element offset of its K column k for weight slab (tap) wi
@@ -202,10 +268,12 @@ __device__ __forceinline__ void cdf_frag_zero(bf16x8_v (&ah)[2][MT], bf16x8_v (&
     }
 }
 // Fragments of k-step ks out of a DMA-filled plane pair (hi at s, lo at s + PLANE): tile rows row + 32 t, t < T, where row = the wave's
-// first row + (lane & 31) and sw = ((lane & 31) >> 2) & 3 its swizzle (tile row offsets are multiples of 32)
-template <int NS, int PLANE, int T>
+// first row + (lane & 31) and sw = ((lane & 31) >> 2) & 3 its swizzle (tile row offsets are multiples of 32).
+// MF = 16: ks is the 16-row half of the 32-row blocks instead, row = the wave's first row + 16 ks + (lane & 15), sw = cdf_swz<16>(row),
+// and the lane's K block is lane >> 4 = 2 half + (l31 >> 4), passed in place of half.
+template <int NS, int PLANE, int T, int MF = 32>
 __device__ __forceinline__ void cdf_read_frags(bf16x8_v (&fh)[T], bf16x8_v (&fl)[T], const unsigned short* s, int ks, int half, int row, int sw) {
-    const int kc = ((ks * 2 + half) ^ sw) * 8;
+    const int kc = ((MF == 16 ? half : ks * 2 + half) ^ sw) * 8;
 #pragma unroll
     for (int t = 0; t < T; ++t) {
         const int off = (row + t * 32) * CDF_SP_RE + kc;
@@ -214,12 +282,13 @@ __device__ __forceinline__ void cdf_read_frags(bf16x8_v (&fh)[T], bf16x8_v (&fl)
     }
 }
 // ... out of a row-pitched halo image: fragment t reads image rows rows[t] + shift (the tap's pixel offset), each with its own swizzle
-template <int NS, int PLANE, int T>
+// (MF = 16: rows[t] belongs to the lane's 16-row half, and `half` is its K block lane >> 4, as above)
+template <int NS, int PLANE, int T, int MF = 32>
 __device__ __forceinline__ void cdf_read_frags_halo(bf16x8_v (&fh)[T], bf16x8_v (&fl)[T], const unsigned short* s, int ks, int half, const int (&rows)[T], int shift) {
 #pragma unroll
     for (int t = 0; t < T; ++t) {
         const int row = rows[t] + shift;
-        const int off = row * CDF_SP_RE + ((ks * 2 + half) ^ ((row >> 2) & 3)) * 8;
+        const int off = row * CDF_SP_RE + ((MF == 16 ? half : ks * 2 + half) ^ cdf_swz<MF>(row)) * 8;
         fh[t] = *(const bf16x8_v*)(s + off);
         if constexpr (NS == 3) fl[t] = *(const bf16x8_v*)(s + PLANE + off);
     }

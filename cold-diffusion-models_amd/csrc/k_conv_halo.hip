@@ -15,9 +15,24 @@
 // Tile = TH = 128 / W full image rows (W = 16, 32, 64 or 128: one tile never straddles two images), so the tile's
 // pixels are the contiguous range [128 tile_m, 128 tile_m + 128) of the flattened pixel index and the epilogue of the
 // generic kernel applies unchanged.  Halo rows outside the image come from the zero page.  8 waves (4 x 2 of 32 x 64).
-// Same XOR swizzle of the 16-byte column by (row >> 2) & 3 on both sides; a lane's 16 fragment rows are consecutive
-// halo rows except at an image-row wrap (+2), where a 2-way bank conflict can occur.
+// XOR swizzle of the 16-byte column by cdf_swz<MF>(row) on both sides (cdf_conv_sp.h).  MF = 32: a lane's 16 fragment rows are
+// consecutive halo rows except at an image-row wrap (+2), where a 2-way bank conflict can occur.  MF = 16: a fragment is 16 consecutive
+// pixels from a multiple of 16, so (16 | W) it never wraps, and its swizzle is conflict-free from any first row.
 // ================================================================================================
+// MFMA shape of the K loop, per kernel form: 32 = v_mfma_f32_32x32x16_bf16, 16 = v_mfma_f32_16x16x32_bf16 (cdf_conv_sp.h).  Same output tile
+// per wave, same register counts, same products per output; the 16 form issues twice as many MFMAs of half the length.  The K loop is
+// matrix-pipe-bound at a clock the chip holds down under load, and the clock it holds depends on the shape: a form is on 16 where that
+// measured faster per launch on random data (profiles/mfma_shape_ab.txt), and keeps no instance of the other shape.
+// MI355X, B = 64, 16 against 32, median of three alternations (the 32 arm's own repetitions spread 0.0 - 0.9 %; NS = 1 at W = 128: 2.5 %):
+//   NS = 3   every W / BN / BM form ahead: 128 -> 64 at 128 pixels +4.2 %, 128 -> 256 and 256 -> 128 at 64 +7.6 %, 256 -> 512 / 512 -> 256 at
+//            32 +6.8 / +8.7 %, 512 -> 1024 / 1024 -> 512 / 1024 -> 2048 at 16 +9.2 / +12.6 / +9.0 %; BM = 128: +3.1 ... +11.5 %; the 64-wide N
+//            tiles +2.9 ... +3.4 % (at B = 16, 1024 -> 512 at 16 pixels: +4.6 %)
+//   NS = 1   W = 64 with BN = 128: 128 -> 256 -1.7 % (BM 256), -1.8 % (BM 128), -3.3 % (B = 16); 256 -> 128 +0.6 / +2.5 / 0.0 % -- no win, stays on 32.
+//            Every other form ahead: W = 128 +4.9 %, W = 32 +3.7 / +7.2 %, W = 16 +5.0 / +6.2 %, the 64-wide N tiles +1.3 ... +6.1 %
+constexpr int cdf_halo_mfma(int W, int BN, int BM, int NS) {
+    (void)BM;
+    return NS == 1 && W == 64 && BN == 128 ? 32 : 16;
+}
 // how many of the halo segments requested in steps t, t-1, ... t-(n-1) (tap index modulo 9) fall on steps with a request (t' < ta)
 constexpr int cdf_halo_parts(int t, int n, int ta) {
     int c = 0;
@@ -28,6 +43,7 @@ constexpr int cdf_halo_parts(int t, int n, int ta) {
 template <int W, int BN, int NB, int BM, int NS = 3>                    // NB weight stages: NB - 1 tap steps requested ahead; BM = 128 or 256 pixels
 __global__ void __launch_bounds__(512, 1) conv_igemm_halo_kernel(SpxArgs a) {
     constexpr int WM = 4, WN = 2, NW = 8, BK = 32, RE = CDF_SP_RE, MT = BM / WM / 32;
+    constexpr int MF = cdf_halo_mfma(W, BN, BM, NS);
     using L = HaloLayout<W, BN, BM>;
     using Segs = typename L::Segs;                                        // 16-row DMA segments of the halo image
     static_assert(NB == L::NB, "the launcher instantiates the stage count of the layout");
@@ -58,7 +74,7 @@ __global__ void __launch_bounds__(512, 1) conv_igemm_halo_kernel(SpxArgs a) {
     // hoisted out of the K loop -- an LDS tap table would put an lgkmcnt(0) wait between the fragment reads and the MFMAs)
 
     // ---- DMA sources.  A: segments Segs::seg(wave, q), q < TA
-    const int srow = cdf_dma_row(lane), q8 = cdf_dma_col(lane);
+    const int srow = cdf_dma_row(lane), q8 = cdf_dma_col<MF>(lane);
     const unsigned short* pa_hi[TA];
     const unsigned short* pa_lo[TA];
     int a_inc[TA], a_seg[TA];
@@ -109,19 +125,24 @@ __global__ void __launch_bounds__(512, 1) conv_igemm_halo_kernel(SpxArgs a) {
     constexpr int NPL = NS == 3 ? 2 : 1;                     // operand planes in flight (hi [, lo])
     constexpr int PB = NPL * SBI, PA = NPL;                  // DMA instructions per wave: one B step, one A segment
 
-    f32x16_t acc[MT][NT];
+    typename cdf_acc_of<MF>::type acc[MT][NT];
     cdf_acc_zero(acc);
 
     const int half = lane >> 5, l31 = lane & 31;
-    // this lane's A fragment rows for tap (0, 0): pixels p = (BM/4) wm + 32 i + l31 of the tile
-    int row0[MT];
+    // this lane's A fragment rows for tap (0, 0): pixels p = (BM/4) wm + 32 i + l31 of the tile (MF = 32: one fragment per k16 step, the
+    // same rows) or p = (BM/4) wm + 32 i + 16 f + (lane & 15), f = 0, 1 (MF = 16: one fragment per 16-row half, all 32 channels)
+    constexpr int NF = MF == 16 ? 2 : 1;
+    const int lrow = MF == 16 ? lane & 15 : l31, kblk = MF == 16 ? lane >> 4 : half;
+    int row0[NF][MT];
 #pragma unroll
-    for (int i = 0; i < MT; ++i) {
-        const int pix = wm * (BM / WM) + i * 32 + l31;
-        const int py = pix / W, px = pix - py * W;
-        row0[i] = (py + 1) * HW2 + px + 1;
-    }
-    const int swb = (l31 >> 2) & 3;                          // B rows: tile-local, multiples of 32 apart
+    for (int f = 0; f < NF; ++f)
+#pragma unroll
+        for (int i = 0; i < MT; ++i) {
+            const int pix = wm * (BM / WM) + i * 32 + f * 16 + lrow;
+            const int py = pix / W, px = pix - py * W;
+            row0[f][i] = (py + 1) * HW2 + px + 1;
+        }
+    const int swb = cdf_swz<MF>(lrow);                       // B rows: tile-local, multiples of 16 apart
 
     // ---- prologue: halo of chunk 0, weights of steps 0 .. NB-2
 #pragma unroll
@@ -151,8 +172,8 @@ __global__ void __launch_bounds__(512, 1) conv_igemm_halo_kernel(SpxArgs a) {
             auto read_frags = [&]() {
 #pragma unroll
                 for (int ks = 0; ks < 2; ++ks) {
-                    cdf_read_frags_halo<NS, PLANE_A>(ah[ks], al[ks], sa, ks, half, row0, tapoff);
-                    cdf_read_frags<NS, PLANE_B>(bh[ks], bl[ks], sb, ks, half, wn * (BN / WN) + l31, swb);
+                    cdf_read_frags_halo<NS, PLANE_A, MT, MF>(ah[ks], al[ks], sa, ks, kblk, row0[MF == 16 ? ks : 0], tapoff);
+                    cdf_read_frags<NS, PLANE_B, NT, MF>(bh[ks], bl[ks], sb, ks, kblk, wn * (BN / WN) + (MF == 16 ? 16 * ks : 0) + lrow, swb);
                 }
             };
             cdf_dephased_step(late, read_frags, mma_frags);
@@ -203,4 +224,22 @@ static int launch_halo_ns(int W, bool n64, int bm, const SpxArgs& a, int M, hipS
 
 int cdf_launch_igemm_halo(int ns, int W, bool n64, int bm, const SpxArgs& a, int M, hipStream_t s, CdfPlan* plan) {
     return ns == 3 ? launch_halo_ns<3>(W, n64, bm, a, M, s, plan) : launch_halo_ns<1>(W, n64, bm, a, M, s, plan);
+}
+
+// cdf_mfma_bf16_16x16x32 (include/colddiff.h): one CDF_MFMA16_BF16 on one wave, operands and result through the lane maps of cdf_conv_sp.h
+__global__ void __launch_bounds__(64) mfma16_probe_kernel(const unsigned short* a, const unsigned short* bt, float* c) {
+    const int lane = threadIdx.x, l15 = lane & 15, quarter = lane >> 4;
+    const bf16x8_v fa = *(const bf16x8_v*)(a + l15 * 32 + quarter * 8), fb = *(const bf16x8_v*)(bt + l15 * 32 + quarter * 8);
+    f32x4_t acc;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) acc[r] = c[cdf_acc_row16(r, quarter) * 16 + l15];
+    acc = CDF_MFMA16_BF16(fa, fb, acc);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) c[cdf_acc_row16(r, quarter) * 16 + l15] = acc[r];
+}
+
+extern "C" int cdf_mfma_bf16_16x16x32(const void* a, const void* bt, float* c, void* stream) {
+    CDF_REQUIRE(a && bt && c && ((uintptr_t)a & 15) == 0 && ((uintptr_t)bt & 15) == 0, "cdf_mfma_bf16_16x16x32: null or misaligned pointer");
+    CDF_LAUNCH(mfma16_probe_kernel, dim3(1), dim3(64), 0, CDF_S, (const unsigned short*)a, (const unsigned short*)bt, c);
+    return cdf_check_launch("mfma16_probe");
 }

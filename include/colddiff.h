@@ -329,6 +329,11 @@ int cdf_conv_wgrad_bf16x_is_row3(int QH, int QW, int CA, int CB, int ntaps, int 
 int cdf_conv_wgrad_bf16x(const void* a_hi, const void* a_lo, int lda, const void* b_hi, const void* b_lo, int ldb, const void* zero,
                          float* ws, int ldo, int B, int QH, int QW, int HA, int WA, int sa, int HB, int WB, int sb, int CA, int CB,
                          int ntaps, const int* tap_desc, int nsplit, float* bsum, const cdf_gemm_tuning* tune, void* stream);
+/* One v_mfma_f32_16x16x32_bf16 product on one wave, through the fragment maps the 16 x 16 x 32 K loops use (csrc/cdf_conv_sp.h: lane l holds
+ * A[l & 15][8 (l >> 4) + j] and Bt[l & 15][8 (l >> 4) + j], j < 8; C register r is row 4 (l >> 4) + r, column l & 15):
+ * c[16][16] += a[16][32] bt[16][32]^T, a and bt bf16 bit patterns, row-major.  A test entry point: it pins the lane maps on the hardware and
+ * the simulator's restatement of the instruction. */
+int cdf_mfma_bf16_16x16x32(const void* a, const void* bt, float* c, void* stream);
 
 /* Device-side input pipeline (replaces Dataset_Aug1 / Dataset + DataLoader, deblurring_diffusion_pytorch.py:983-1026, 1094-1096).
  * cache: [N][S][S][C] uint8 (NHWC) images already resized to S = int(1.12 image_size) (the deterministic Resize of the reference's
