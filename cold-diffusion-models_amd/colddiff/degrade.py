@@ -52,17 +52,23 @@ def _steps(t, B):
     return t.to(torch.int64).contiguous()
 
 
+def _chain_io(x, t, img, want_snap):
+    """The prologue every chain shares: the contiguous fp32 image, its shape, the per-row step table, y, snap (only when wanted) and
+    the converted img -- returned so that the caller keeps it alive over the launch."""
+    x = _img(x)
+    t = _steps(t, x.shape[0])
+    y = torch.empty_like(x)
+    snap = torch.empty_like(x) if want_snap else None
+    img = None if img is None else _img(img)
+    return x, x.shape, t, y, snap, img
+
+
 def blur_chain(x, taps, k, pad_mode, t=None, step_lo=0, step_hi=0, img=None, want_prev=False, collapse_step=-1, quantise=False,
                taps1d=None):
     """Apply blur steps step_lo..hi(b) (hi = t[b] or step_hi) with the plane resident in LDS.
     Returns y (or the Alg.2 combination img - D_hi + D_{hi-1} when img is given) [, D_{hi-1}].
     taps1d ([T, C, 2, k], see separable_taps) selects the separable kernel: 2k instead of k*k FMAs per pixel."""
-    x = _img(x)
-    B, C, H, W = x.shape
-    t = _steps(t, B)
-    y = torch.empty_like(x)
-    snap = torch.empty_like(x) if want_prev else None
-    img = None if img is None else _img(img)     # keep the (possibly converted) tensor alive over the launch
+    x, (B, C, H, W), t, y, snap, img = _chain_io(x, t, img, want_prev)
     L = rt.lib()
     if taps1d is not None and k <= 64 and k // 2 < min(H, W) and L.cdf_blur_sep_lds_bytes(H, W) <= 160 * 1024:
         L.cdf_blur_chain_sep(P(x), P(y), P(snap), P(img), P(taps1d), P(t), B, C, H, W, k, step_lo, step_hi,
@@ -107,26 +113,16 @@ def plane_mean_(x):
 
 
 def mask_chain(x, masks, t=None, step_lo=0, step_hi=0, img=None, off_y=None, off_x=None, quantise=False):
-    x = _img(x)
-    B, C, H, W = x.shape
-    t = _steps(t, B)
+    x, (B, C, H, W), t, y, snap, img = _chain_io(x, t, img, img is not None)
     off_y, off_x = _steps(off_y, B), _steps(off_x, B)
-    y = torch.empty_like(x)
-    snap = torch.empty_like(x) if img is not None else None
-    img = None if img is None else _img(img)
     rt.lib().cdf_mask_chain(P(x), P(y), P(snap), P(img), P(masks), P(t), P(off_y), P(off_x), B, C, H, W,
                             masks.shape[1], masks.shape[2], step_lo, step_hi, 1 if quantise else 0, rt.stream(x))
     return y
 
 
 def pixelate_chain(x, sizes, mode, t=None, step_lo=0, step_hi=0, img=None):
-    x = _img(x)
-    B, C, H, W = x.shape
-    t = _steps(t, B)
+    x, (B, C, H, W), t, y, snap, img = _chain_io(x, t, img, img is not None)
     assert H == W, "the resolution operator works on square images (as the reference asserts)"
-    y = torch.empty_like(x)
-    snap = torch.empty_like(x) if img is not None else None
-    img = None if img is None else _img(img)
     rt.lib().cdf_pixelate_chain(P(x), P(y), P(snap), P(img), P(sizes), P(t), B, C, H, step_lo, step_hi,
                                 mode, rt.stream(x))
     return y

@@ -337,6 +337,14 @@ static inline int cdf_ew_grid4k(long long n) {               // blocks of 256 th
     if (g > 4096) g = 4096;
     return g < 1 ? 1 : (int)g;
 }
+static inline int cdf_ew_grid8k(long long n) {               // ... at most 8192
+    long long g = (n + 255) / 256;
+    if (g > 8192) g = 8192;
+    return g < 1 ? 1 : (int)g;
+}
+// the grid-stride loop of those launches: i = this thread's elements of [0, n)
+#define CDF_EW_LOOP(i, n) \
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (long long)gridDim.x * blockDim.x)
 
 // XCD-aware work order.  Workgroups are handed to the 8 XCDs (each with its own 4 MB L2) round-robin in dispatch order, so
 // work items that are neighbours in memory -- adjacent image tiles with a shared halo, the taps of one pixel range -- land on 8
@@ -378,6 +386,22 @@ __device__ __forceinline__ float cdf_wave_max(float v) {
 __device__ __forceinline__ float cdf_group_sum(float v, int width) {
     for (int o = width >> 1; o > 0; o >>= 1) v += __shfl_xor(v, o);
     return v;
+}
+// The fp32 sum of v over a block (blockDim.x a multiple of 64, <= 1024): wave sums, then the waves' partials added in wave order by
+// thread 0; every thread gets the total.  red = 17 floats of LDS.
+__device__ __forceinline__ float cdf_block_sum(float v, float* red) {
+    v = cdf_wave_sum(v);
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
+    __syncthreads();
+    if (lane == 0) red[w] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float s = 0.f;
+        for (int i = 0; i < nw; ++i) s += red[i];
+        red[16] = s;
+    }
+    __syncthreads();
+    return red[16];
 }
 // The fp64 sum of v over a block of 256 threads, the same tree whatever the values (two runs are bit-identical); every thread gets the
 // total.  red = 256 doubles of LDS nobody else is reading.  (Here and not in cdf_f64_tile.h: it knows nothing of the tile form, and four of

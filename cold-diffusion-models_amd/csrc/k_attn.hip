@@ -426,17 +426,11 @@ extern "C" int cdf_linattn_dcontext(const float* qkv, int ld, const float* dout,
     return cdf_check_launch("linattn_dcontext");
 }
 
-static inline int la_grid(long long n) {
-    long long g = (n + 255) / 256;
-    if (g > 8192) g = 8192;
-    return g < 1 ? 1 : (int)g;
-}
-
 extern "C" int cdf_linattn_softk(const float* qkv, int ld, const float* kmax, const float* ksum, float* pn, int ldp, int B,
                                  int n, int heads, void* stream) {
     CDF_REQUIRE(qkv && kmax && ksum && pn && ld % 4 == 0 && ldp % 4 == 0, "cdf_linattn_softk: bad args");
     const int HD = heads * LA_D;
-    CDF_LAUNCH(linattn_softk_kernel, dim3(la_grid((long long)B * n * HD / 4)), dim3(256), 0, CDF_S, qkv, ld, kmax, ksum, pn, ldp, B, n, HD);
+    CDF_LAUNCH(linattn_softk_kernel, dim3(cdf_ew_grid8k((long long)B * n * HD / 4)), dim3(256), 0, CDF_S, qkv, ld, kmax, ksum, pn, ldp, B, n, HD);
     return cdf_check_launch("linattn_softk");
 }
 
@@ -444,7 +438,7 @@ extern "C" int cdf_linattn_dk(const float* pn, int ldp, const float* dp, int ldd
                               int B, int n, int heads, void* stream) {
     CDF_REQUIRE(pn && dp && rvec && dk && ldp % 4 == 0 && lddp % 4 == 0 && lddk % 4 == 0, "cdf_linattn_dk: bad args");
     const int HD = heads * LA_D;
-    CDF_LAUNCH(linattn_dk_kernel, dim3(la_grid((long long)B * n * HD / 4)), dim3(256), 0, CDF_S, pn, ldp, dp, lddp, rvec, dk, lddk, B, n, HD);
+    CDF_LAUNCH(linattn_dk_kernel, dim3(cdf_ew_grid8k((long long)B * n * HD / 4)), dim3(256), 0, CDF_S, pn, ldp, dp, lddp, rvec, dk, lddk, B, n, HD);
     return cdf_check_launch("linattn_dk");
 }
 

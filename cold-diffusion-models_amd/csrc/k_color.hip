@@ -234,20 +234,9 @@ __global__ void __launch_bounds__(256) lab_convert_kernel(const float* x, float*
 // ---- per-image mean shift ------------------------------------------------------------------------------------------------------------
 #define CDF_MS_CHUNK 8192          // elements of one image per block
 
-__device__ __forceinline__ float cdf_color_block_sum(float v, float* red /* >= 5 floats of LDS */) {
-    v = cdf_wave_sum(v);
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane == 0) red[wv] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) red[4] = ((red[0] + red[1]) + red[2]) + red[3];
-    __syncthreads();
-    return red[4];
-}
-
 // stage 1: ws[(b * nchunk + chunk) * 2 + {0, 1}] = the chunk's sums of x and y (x nullable: 0)
 __global__ void __launch_bounds__(256) mean_shift_partial_kernel(const float* x, const float* y, float* ws, long long n, int nchunk) {
-    __shared__ float red[8];
+    __shared__ float red[32];                                           // (cdf_block_sum: 17 floats)
     const int b = blockIdx.y, ch = blockIdx.x;
     const long long lo = (long long)ch * CDF_MS_CHUNK;
     const long long hi = lo + CDF_MS_CHUNK < n ? lo + CDF_MS_CHUNK : n;
@@ -257,8 +246,8 @@ __global__ void __launch_bounds__(256) mean_shift_partial_kernel(const float* x,
         sy += y[base + i];
         if (x) sx += x[base + i];
     }
-    const float ty = cdf_color_block_sum(sy, red);
-    const float tx = cdf_color_block_sum(sx, red);
+    const float ty = cdf_block_sum(sy, red);
+    const float tx = cdf_block_sum(sx, red);
     if (threadIdx.x == 0) {
         ws[((size_t)b * nchunk + ch) * 2] = tx;
         ws[((size_t)b * nchunk + ch) * 2 + 1] = ty;

@@ -8,14 +8,6 @@
 #include "cdf_common.h"
 #include "colddiff.h"
 
-static inline int ew_grid(long long n) {
-    long long g = (n + 255) / 256;
-    if (g > 8192) g = 8192;
-    return g < 1 ? 1 : (int)g;
-}
-#define CDF_EW_LOOP(i, n) \
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (long long)gridDim.x * blockDim.x)
-
 // emb[b][j] = sin(t[b] * f_j), emb[b][half + j] = cos(t[b] * f_j); the frequency table
 // f_j = exp(-j * ln(10000)/(half-1)) is an init-time constant supplied by the caller (a 1e-7 relative
 // difference in f_j is amplified by t ~ 1000 into a 1e-4 phase error, so it is taken as data).
@@ -238,7 +230,7 @@ __global__ void __launch_bounds__(256) linear_small_wgrad_kernel(const float* dy
 
 extern "C" int cdf_sinusoidal(const int64_t* t, const float* freq, float* out, int ldo, int B, int dim, void* stream) {
     CDF_REQUIRE(t && freq && out && B > 0 && dim >= 4 && (dim & 1) == 0 && ldo >= dim, "cdf_sinusoidal: bad args");
-    CDF_LAUNCH(sinusoidal_kernel, dim3(ew_grid((long long)B * dim / 2)), dim3(256), 0, CDF_S, t, freq, out, ldo, B, dim);
+    CDF_LAUNCH(sinusoidal_kernel, dim3(cdf_ew_grid8k((long long)B * dim / 2)), dim3(256), 0, CDF_S, t, freq, out, ldo, B, dim);
     return cdf_check_launch("sinusoidal");
 }
 extern "C" int cdf_linear_small(const float* in, int ldi, const float* Wm, int ldw, const float* bias, float* out, int ldo, int M,
@@ -261,36 +253,36 @@ extern "C" int cdf_linear_small_wgrad(const float* dy, int ldd, const float* x, 
 
 extern "C" int cdf_act_fwd(const float* x, int ldx, float* y, int ldy, long long rows, int C, int act, void* stream) {
     CDF_REQUIRE(x && y && rows > 0 && C > 0 && act >= 1 && act <= 3, "cdf_act_fwd: bad args");
-    CDF_LAUNCH(act_fwd_kernel, dim3(ew_grid(rows * C)), dim3(256), 0, CDF_S, x, ldx, y, ldy, rows, C, act);
+    CDF_LAUNCH(act_fwd_kernel, dim3(cdf_ew_grid8k(rows * C)), dim3(256), 0, CDF_S, x, ldx, y, ldy, rows, C, act);
     return cdf_check_launch("act_fwd");
 }
 extern "C" int cdf_act_bwd(const float* x, int ldx, const float* dy, int lddy, float* dx, int lddx, long long rows, int C,
                            int act, int accumulate, void* stream) {
     CDF_REQUIRE(x && dy && dx && rows > 0 && C > 0 && (act == 1 || act == 2), "cdf_act_bwd: bad args");
-    CDF_LAUNCH(act_bwd_kernel, dim3(ew_grid(rows * C)), dim3(256), 0, CDF_S, x, ldx, dy, lddy, dx, lddx, rows, C, act, accumulate);
+    CDF_LAUNCH(act_bwd_kernel, dim3(cdf_ew_grid8k(rows * C)), dim3(256), 0, CDF_S, x, ldx, dy, lddy, dx, lddx, rows, C, act, accumulate);
     return cdf_check_launch("act_bwd");
 }
 extern "C" int cdf_axpby(float* dst, int ldd, const float* src, int lds, long long rows, int C, float alpha, float beta,
                          void* stream) {
     CDF_REQUIRE(dst && src && rows > 0 && C > 0, "cdf_axpby: bad args");
-    CDF_LAUNCH(axpby_kernel, dim3(ew_grid(rows * C)), dim3(256), 0, CDF_S, dst, ldd, src, lds, rows, C, alpha, beta);
+    CDF_LAUNCH(axpby_kernel, dim3(cdf_ew_grid8k(rows * C)), dim3(256), 0, CDF_S, dst, ldd, src, lds, rows, C, alpha, beta);
     return cdf_check_launch("axpby");
 }
 extern "C" int cdf_upsample2(const float* x, int ldx, float* y, int ldy, int B, int H, int W, int C, void* stream) {
     CDF_REQUIRE(x && y && C % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0, "cdf_upsample2: bad args");
-    CDF_LAUNCH(upsample2_kernel, dim3(ew_grid((long long)B * 4 * H * W * (C / 4))), dim3(256), 0, CDF_S, x, ldx, y, ldy, B, H, W, C / 4);
+    CDF_LAUNCH(upsample2_kernel, dim3(cdf_ew_grid8k((long long)B * 4 * H * W * (C / 4))), dim3(256), 0, CDF_S, x, ldx, y, ldy, B, H, W, C / 4);
     return cdf_check_launch("upsample2");
 }
 extern "C" int cdf_upsample2_bwd(const float* dy, int lddy, float* dx, int lddx, int B, int H, int W, int C,
                                  int accumulate, void* stream) {
     CDF_REQUIRE(dy && dx && C % 4 == 0 && lddy % 4 == 0 && lddx % 4 == 0, "cdf_upsample2_bwd: bad args");
-    CDF_LAUNCH(upsample2_bwd_kernel, dim3(ew_grid((long long)B * H * W * (C / 4))), dim3(256), 0, CDF_S, dy, lddy, dx, lddx, B, H, W, C / 4, accumulate);
+    CDF_LAUNCH(upsample2_bwd_kernel, dim3(cdf_ew_grid8k((long long)B * H * W * (C / 4))), dim3(256), 0, CDF_S, dy, lddy, dx, lddx, B, H, W, C / 4, accumulate);
     return cdf_check_launch("upsample2_bwd");
 }
 extern "C" int cdf_dropout(const float* x, int ldx, float* y, int ldy, long long rows, int C, float p,
                            long long seed, void* stream) {
     CDF_REQUIRE(x && y && rows > 0 && C > 0 && p >= 0.f && p < 1.f, "cdf_dropout: bad args");
-    CDF_LAUNCH(dropout_kernel, dim3(ew_grid(rows * C)), dim3(256), 0, CDF_S, x, ldx, y, ldy, rows, C, p, (unsigned long long)seed);
+    CDF_LAUNCH(dropout_kernel, dim3(cdf_ew_grid8k(rows * C)), dim3(256), 0, CDF_S, x, ldx, y, ldy, rows, C, p, (unsigned long long)seed);
     return cdf_check_launch("dropout");
 }
 extern "C" int cdf_adam_step(float* p, const float* g, float* m, float* v, long long n, double lr, double beta1,
@@ -298,18 +290,18 @@ extern "C" int cdf_adam_step(float* p, const float* g, float* m, float* v, long 
     CDF_REQUIRE(p && g && m && v && n > 0 && step >= 1, "cdf_adam_step: bad args");
     const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
     const double step_size = lr / bc1;
-    CDF_LAUNCH(adam_kernel, dim3(ew_grid(n)), dim3(256), 0, CDF_S, p, g, m, v, n, (float)(1.0 - beta1), (float)beta2,
+    CDF_LAUNCH(adam_kernel, dim3(cdf_ew_grid8k(n)), dim3(256), 0, CDF_S, p, g, m, v, n, (float)(1.0 - beta1), (float)beta2,
                (float)(1.0 - beta2), (float)(-step_size), (float)sqrt(bc2), (float)eps);
     return cdf_check_launch("adam");
 }
 extern "C" int cdf_ema_update(float* ma, const float* p, long long n, double beta, void* stream) {
     CDF_REQUIRE(ma && p && n > 0, "cdf_ema_update: bad args");
-    CDF_LAUNCH(ema_kernel, dim3(ew_grid(n)), dim3(256), 0, CDF_S, ma, p, n, (float)beta, (float)(1.0 - beta));
+    CDF_LAUNCH(ema_kernel, dim3(cdf_ew_grid8k(n)), dim3(256), 0, CDF_S, ma, p, n, (float)beta, (float)(1.0 - beta));
     return cdf_check_launch("ema");
 }
 extern "C" int cdf_scale(float* x, long long n, float s, void* stream) {
     CDF_REQUIRE(x && n > 0, "cdf_scale: bad args");
-    CDF_LAUNCH(scale_kernel, dim3(ew_grid(n)), dim3(256), 0, CDF_S, x, n, s);
+    CDF_LAUNCH(scale_kernel, dim3(cdf_ew_grid8k(n)), dim3(256), 0, CDF_S, x, n, s);
     return cdf_check_launch("scale");
 }
 extern "C" int cdf_zero(void* p, long long bytes, void* stream) {

@@ -184,6 +184,10 @@ BLUR_CASES = [  # H, W, k, pad, C, step_lo
     (128, 128, 11, "circular", 2, 2),        # 142,944 B
     (128, 124, 5, "reflect", 2, 1),
     (8, 16, 27, "circular", 3, 3),           # dense only: the halo wraps more than once
+    # H % 4 == 2: the separable kernel's one-row strip form at a compile-time k, inner and border strips in one row
+    (10, 12, 3, "reflect", 2, 1),            # reach 4: the strip at x0 = 4 is inner, the others are border
+    (18, 24, 11, "circular", 3, 0),          # reach 8: strips at x0 = 8, 12 are inner
+    (14, 24, 15, "reflect", 2, 2),           # reach 8, k / 2 = 7 < 14
 ]
 
 
