@@ -337,9 +337,10 @@ __global__ void __launch_bounds__(256) tapsum3_kernel(const float* z, int ldz, f
 }
 
 extern "C" int cdf_conv_cin4_tapsum3(const float* z, int ldz, float* dx, int B, int H, int W, int Cin, int accumulate, void* stream) {
-    CDF_REQUIRE(z && dx && B > 0 && H > 0 && W > 0 && Cin >= 1 && Cin <= 4 && ldz >= 9 * Cin && ldz % 4 == 0 && ldz <= 64 &&
+    CDF_REQUIRE(z && dx && B > 0 && H > 0 && W > 0 && Cin >= 1 && Cin <= 4 && ldz >= 9 * Cin && ldz % 4 == 0 && ldz <= 48 &&
                 ((((uintptr_t)dx) | ((uintptr_t)z)) & 15) == 0,
-                "cdf_conv_cin4_tapsum3: 1..4 input channels, z rows hold 9 Cin values with a pitch % 4 == 0, dx is [B,H,W,4], both 16-byte aligned");
+                "cdf_conv_cin4_tapsum3: 1..4 input channels, z rows hold 9 Cin values with a pitch that is a multiple of 4 and <= 48 (the 18 x 18 halo of z rows "
+                "is 62,208 B of LDS there; 52 would be 67,392 B, past the 64 KB of a plain launch), dx is [B,H,W,4], both 16-byte aligned");
     const int tiles_x = cdf_cdiv(W, TS_T), tiles_y = cdf_cdiv(H, TS_T);
     const size_t lds = (size_t)(TS_T + 2) * (TS_T + 2) * ldz * sizeof(float);
     CDF_LAUNCH(tapsum3_kernel, dim3((unsigned)(tiles_x * tiles_y * B)), dim3(256), lds, CDF_S, z, ldz, dx, H, W, Cin, accumulate, tiles_x, tiles_y);

@@ -669,7 +669,8 @@ int cdf_conv_cin4_dgrad(const float* dy, int ldd, const float* w, int ldw, float
                         void* stream);
 /* Second stage of the two-stage 3x3 data gradient (first stage: the 1x1 GEMM z[q][c*9 + ky*3 + kx] = sum_co dy[q][co] W[co][c][ky][kx],
  * whose [Cout][9 Cin] weight matrix is the parameter in its PyTorch layout):  dx[p][c] (+)= sum_{ky,kx} z[p - (ky-1, kx-1)][c*9 + ky*3 + kx],
- * zero outside the image; dx is [B,H,W,4] (channels >= Cin zero), z rows have pitch ldz >= 9 Cin (ldz % 4 == 0, <= 64). */
+ * zero outside the image; dx is [B,H,W,4] (channels >= Cin zero), z rows have pitch ldz >= 9 Cin (ldz % 4 == 0, <= 48: the
+ * 18 x 18 halo of z rows a block holds in LDS is 62,208 B there, and a plain launch gets 64 KB). */
 int cdf_conv_cin4_tapsum3(const float* z, int ldz, float* dx, int B, int H, int W, int Cin, int accumulate, void* stream);
 int cdf_conv_cin4_nchunk(long long M);
 int cdf_conv_cin4_wgrad(const float* x, const float* dy, int ldd, float* part, float* bsum, int B, int H, int W, int Cin, int Cout,

@@ -273,6 +273,26 @@ for _names, _test in ((("cdf_dwconv7", "cdf_dwconv7_io", "cdf_dwconv7_planes"), 
 _IF = "test_inception_forms.py::"
 COVERED_AT_PRODUCTION_SHAPE["cdf_conv_gemm_bf16"] += [_IF + "test_extractor_sp_forms", _IF + "test_extractor_sp_production_shapes"]
 COVERED_AT_PRODUCTION_SHAPE["cdf_conv_gemm"] += [_IF + "test_extractor_f32_forms", _IF + "test_extractor_f32_production_shapes"]
+# the image-side direct convolutions, the slab reductions and the column sums: every null-output, pitch, accumulate, stride and kernel /
+# chunk form the product launches (test_coverage_guard holds the recordings against that module's form tables)
+_SK = "test_side_kernel_forms.py::"
+for _names, _test in ((("cdf_conv_cin4_fwd",), "test_cin4_fwd_forms"), (("cdf_conv_cin4_dgrad",), "test_cin4_dgrad_forms"),
+                      (("cdf_conv_cin4_tapsum3",), "test_cin4_tapsum3_forms"), (("cdf_conv_cin4_wgrad", "cdf_conv_cin4_nchunk"), "test_cin4_wgrad_forms"),
+                      (("cdf_unpack_reduce", "cdf_unpack_reduce_bias"), "test_unpack_reduce_forms"),
+                      (("cdf_colsum", "cdf_colsum_io", "cdf_colsum_nchunk"), "test_colsum_forms")):
+    for _name in _names:
+        COVERED_AT_PRODUCTION_SHAPE[_name].append(_SK + _test)
+# ... and linear attention and the attention block's row softmax (test_side_kernel_forms_attn.py), the same way
+_SA = "test_side_kernel_forms_attn.py::"
+for _names, _test in ((("cdf_linattn_context", "cdf_linattn_nsplit", "cdf_linattn_ws_floats"), "test_linattn_context_forms"),
+                      (("cdf_linattn_dcontext",), "test_linattn_dcontext_forms"), (("cdf_linattn_bwd_kv", "cdf_linattn_bwd_kv_planes"), "test_linattn_bwd_kv_forms"),
+                      (("cdf_linattn_kvctx", "cdf_linattn_kvctx_parts"), "test_linattn_kvctx_forms"),
+                      (("cdf_linattn_finalize",), "test_linattn_finalize_forms"), (("cdf_linattn_dctx_finish",), "test_linattn_dctx_finish_forms"),
+                      (("cdf_linattn_softk", "cdf_linattn_dk"), "test_linattn_softk_dk_forms")):
+    for _name in _names:
+        COVERED_AT_PRODUCTION_SHAPE[_name].append(_SA + _test)
+for _name in ("cdf_softmax_rows_fwd", "cdf_softmax_rows_bwd"):
+    COVERED_AT_PRODUCTION_SHAPE[_name] = [_SA + "test_softmax_rows_forms"]
 # entry points with nothing shape-dependent to test at scale, with the reason
 EXEMPT = {
     "cdf_last_error": "host-side error string",
@@ -297,6 +317,15 @@ _NORM_DW = ("cdf_dwconv7", "cdf_dwconv7_io", "cdf_dwconv7_planes", "cdf_dwconv7_
             "cdf_layernorm_c_fwd_io", "cdf_layernorm_c_bwd", "cdf_layernorm_c_bwd_io", "cdf_layernorm_c_bwd_planes", "cdf_groupnorm_fwd",
             "cdf_groupnorm_fwd_ex", "cdf_groupnorm_bwd", "cdf_groupnorm_bwd_ex")
 _GEMM_FAMILY += _NORM_DW
+# the image-side direct convolutions (csrc/k_conv_cin4.hip) and the reductions (csrc/k_reduce.hip): guarded form by form too
+# (test_side_kernel_forms.py); their calls are kept with the GEMM calls as well
+_SIDE = ("cdf_conv_cin4_fwd", "cdf_conv_cin4_dgrad", "cdf_conv_cin4_tapsum3", "cdf_conv_cin4_wgrad", "cdf_unpack_reduce", "cdf_unpack_reduce_bias",
+         "cdf_colsum", "cdf_colsum_io")
+# ... and linear attention and the row softmax (csrc/k_attn.hip, csrc/k_attn_kvctx.hip; test_side_kernel_forms_attn.py)
+_SIDE_ATTN = ("cdf_linattn_context", "cdf_linattn_dcontext", "cdf_linattn_bwd_kv", "cdf_linattn_bwd_kv_planes", "cdf_linattn_kvctx", "cdf_linattn_finalize",
+              "cdf_linattn_dctx_finish", "cdf_linattn_softk", "cdf_linattn_dk", "cdf_softmax_rows_fwd", "cdf_softmax_rows_bwd")
+_SIDE += _SIDE_ATTN
+_GEMM_FAMILY += _SIDE
 
 
 def _guard_calls(bench_data):
@@ -304,7 +333,8 @@ def _guard_calls(bench_data):
     stream) and of one sampler step: (set of names, the (nsplit, T, R, C) of the bf16x3 step's slab reductions, the (recording, name,
     arguments) of every GEMM / weight-gradient call (pre-split family, exact-fp32 pair, in-kernel-split pair) and of every depthwise,
     LayerNorm and GroupNorm call (_NORM_DW) of those and of one forward + backward pass of config 2's network (dropout 0.1, training mode)
-    -- the phase / tap descriptors copied, they are buffers the caller may reuse)."""
+    -- the phase / tap descriptors copied, they are buffers the caller may reuse; and of every image-side direct convolution, slab
+    reduction and column sum (_SIDE) of the same four runs)."""
     from colddiff import runtime as rt
     names, unpack, gemm = set(), set(), []
 
@@ -363,6 +393,8 @@ def test_coverage_guard(bench_data):
     of that module's case tables has, and the forms it flags as reached must still be reached.  The in-kernel-split pair
     (cdf_conv_gemm_bf16, cdf_conv_wgrad_bf16) the same way against test_gemm_sp_forms (sp_gemm_form / sp_wgrad_form).  The depthwise,
     LayerNorm and GroupNorm entry points (_NORM_DW) the same way against the six classifiers and case tables of test_norm_dw_forms.
+    The image-side direct convolutions, the slab reductions, the column sums, linear attention and the row softmax (_SIDE) the same way
+    against the classifiers and case tables of test_side_kernel_forms and test_side_kernel_forms_attn.
     The FID extractor is a recording of its own (test_inception_forms.extractor_calls: none of the four runs above launches it): the forms
     of its cdf_conv_gemm_bf16 / cdf_conv_gemm calls the same way against test_inception_forms' tables (check_recording)."""
     import os
@@ -388,7 +420,7 @@ def test_coverage_guard(bench_data):
         if name == "cdf_conv_wgrad_bf16x":
             reached_w.setdefault((_wgrad_code(L, name, a), 3 if a[1] else 1), (src, a[9:21], a[22]))
             rows_w.add(gp.wgrad_row(name, a))
-        elif name != "cdf_conv_wgrad" and name not in _F32_GEMM and name not in _SP_GEMM and name not in _NORM_DW:
+        elif name != "cdf_conv_wgrad" and name not in _F32_GEMM and name not in _SP_GEMM and name not in _NORM_DW and name not in _SIDE:
             reached_g.setdefault((_gemm_code(L, name, a), 3 if a[1] else 1), (src, name, a[9:21]))
             rows_g.add(gp.gemm_row(name, a))
     assert all(c > 0 for c, _ in list(reached_g) + list(reached_w)), (reached_g, reached_w)
@@ -454,6 +486,21 @@ def test_coverage_guard(bench_data):
         assert not untested, "%s forms the product reaches without a test_norm_dw_forms row: %s" % (what, untested)
         stale = sorted(flagged - set(reached), key=repr)
         assert not stale, "test_norm_dw_forms flags %s forms as reached that the recordings no longer contain: %s" % (what, stale)
+    # ---- the image-side direct convolutions, the slab reductions and the column sums (k_conv_cin4.hip, k_reduce.hip), linear attention and the
+    # row softmax (k_attn.hip, k_attn_kvctx.hip), form by form
+    import test_side_kernel_forms as sk
+    import test_side_kernel_forms_attn as sa
+    assert set(sk.ALL_NAMES) | set(sa.ALL_NAMES) == set(_SIDE) and set(sa.ALL_NAMES) == set(_SIDE_ATTN)
+    for mod, what, reached in [(m, w, r) for m in (sk, sa) for w, r in m.reached_forms(gemm).items()]:
+        tested, flagged = mod.forms_of_rows(what), mod.REACHED[what]
+        print("%s forms reached:" % what)
+        for k in sorted(reached, key=repr):
+            print("    %r," % (k,))
+        assert reached or not flagged, what
+        untested = {k: v for k, v in reached.items() if k not in tested}
+        assert not untested, "%s forms the product reaches without a %s row: %s" % (what, mod.__name__, untested)
+        stale = sorted(flagged - set(reached), key=repr)
+        assert not stale, "%s flags %s forms as reached that the recordings no longer contain: %s" % (mod.__name__, what, stale)
     # ---- the FID extractor's conv GEMM launches (colddiff/inception.py), form by form: one forward on 64 x 64 images at B = 50 and B = 1 in
     # the default mode, in bf16 and in f32 -- every recorded form must have a row in test_inception_forms, every form it flags is recorded
     import test_inception_forms as tif
