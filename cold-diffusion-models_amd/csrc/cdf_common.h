@@ -158,6 +158,11 @@ __device__ __forceinline__ void cdf_acc_stage(float* tile, int pitch, int row0, 
 #pragma unroll
             for (int r = 0; r < 4; ++r) tile[(row0 + 16 * a + cdf_acc_row16(r, quarter)) * pitch + col0 + 16 * b + l15] = acc.q[a][b][r];
 }
+template <int NT>
+__device__ __forceinline__ void cdf_acc_stage(float* tile, int pitch, int row0, int col0, const f32x4q_t (&acc)[NT], int half, int l31) {
+#pragma unroll
+    for (int j = 0; j < NT; ++j) cdf_acc_stage(tile, pitch, row0, col0 + j * 32, acc[j], half, l31);
+}
 template <int MT, int NT>
 __device__ __forceinline__ void cdf_acc_stage(float* tile, int pitch, int row0, int col0, const f32x4q_t (&acc)[MT][NT], int half, int l31) {
 #pragma unroll

@@ -55,6 +55,16 @@ __device__ __forceinline__ bf16x4_v cdf_lds_read_tr16(const unsigned short* p) {
 #endif
 // One operand's MFMA fragment out of a pixel-major tile: 8 consecutive pixels (two transposing reads, 4 rows apart) of the lane's channel, hi
 // plane and -- NS == 3 -- the lo plane `plane` elements behind it.
+// (p0: the lane's address in the block of pixels 0..3, p1: in the block of pixels 4..7)
+template <int NS>
+__device__ __forceinline__ void cdf_tr_frag2(const unsigned short* p0, const unsigned short* p1, int plane, bf16x8_v& hi, bf16x8_v& lo) {
+    const bf16x4_v h0 = cdf_lds_read_tr16(p0), h1 = cdf_lds_read_tr16(p1);
+    hi = __builtin_shufflevector(h0, h1, 0, 1, 2, 3, 4, 5, 6, 7);
+    if constexpr (NS == 3) {
+        const bf16x4_v l0 = cdf_lds_read_tr16(p0 + plane), l1 = cdf_lds_read_tr16(p1 + plane);
+        lo = __builtin_shufflevector(l0, l1, 0, 1, 2, 3, 4, 5, 6, 7);
+    }
+}
 template <int NS>
 __device__ __forceinline__ void cdf_tr_frag(const unsigned short* p, int plane, int pitch, bf16x8_v& hi, bf16x8_v& lo) {
     const bf16x4_v h0 = cdf_lds_read_tr16(p), h1 = cdf_lds_read_tr16(p + 4 * pitch);
@@ -63,6 +73,26 @@ __device__ __forceinline__ void cdf_tr_frag(const unsigned short* p, int plane, 
         const bf16x4_v l0 = cdf_lds_read_tr16(p + plane), l1 = cdf_lds_read_tr16(p + plane + 4 * pitch);
         lo = __builtin_shufflevector(l0, l1, 0, 1, 2, 3, 4, 5, 6, 7);
     }
+}
+// The pixel-major tile image [px][pitch = T + 32] bf16 (T = 64 or 128 channels) of the weight-gradient kernels, by the MFMA shape MF of the K loop
+// that reads it: element (row, col) lives at cdf_px_off<MF>(row, col, pitch), for the ds_write_b128 that fills it and for every transposing read.
+//   MF = 32: plain.  The 16-lane group g of a fragment read takes the [4 px][16 ch] block at pixels 8 (g >> 1) + {0, 4}, channels 16 (g & 1): the
+//     32 lanes the LDS serves together are 4 rows x 64 contiguous bytes, the rows 16 banks apart (pitch 80 or 48 dwords): all 64 banks once.
+//   MF = 16: lane l of v_mfma_f32_16x16x32_bf16 holds channel l & 15 at pixels 8 (l >> 4) .. +7 -- both operands, both are pixel-major -- so group
+//     g takes pixels 8 g + {0, 4} of ONE 16-channel block, and the two groups of a 32-lane pass are 4 rows x 32 bytes each, 8 pixel rows apart.
+//     8 pitches are 0 modulo the 64 banks (so are 8 rows of any 16-byte-aligned pitch that keeps the 4 rows of a group apart): 2-way.  The rows of
+//     the two groups, r and r + 8, always differ in bit 3, so XORing bit 3 of the row into bit 4 of the column (in elements: it swaps the 32-byte
+//     halves of a 64-byte column block; in 16-byte chunks, chunk ^ ((row >> 3) & 1) << 1) moves one group 8 banks away from the other, from any
+//     first row (the row-of-taps kernel reads X at row + 1 + dx): 4 rows x 2 groups x 8 banks, all 64 once.  A 16-byte store chunk and the 8-byte
+//     read piece both stay inside their 32-byte half, and the swap stays inside one 32-channel block.  The swap depends on the row: rows r and
+//     r + 4 of one fragment can sit in different halves, so every address comes from this function, never from base + q * pitch.
+//     Measured (conv_wgrad_row3_kernel<128, 128, 3>, 256 -> 256 at 64 pixels, B = 64): SQ_LDS_BANK_CONFLICT 0 with MF = 32, 1.3 % of
+//     SQ_LDS_IDX_ACTIVE with MF = 16 -- not zero; which access keeps a conflict is open (profiles/wgrad_mfma_shape_ab.txt, section 5).
+// (col0: a multiple of 32 -- a wave's first column -- that the swap leaves alone; added first, the order the MF = 32 kernels were tuned with: one
+//  of them sits exactly at the 128 registers of four waves per SIMD and goes over with the sum associated the other way)
+template <int MF>
+__device__ __forceinline__ int cdf_px_off(int row, int col, int pitch, int col0 = 0) {
+    return row * pitch + col0 + (MF == 16 ? col ^ (((row >> 3) & 1) << 4) : col);
 }
 
 // Block tile BM x BN, WM x WN waves of (BM/WM) x (BN/WN): the whole tile goes through LDS in one pass (cdf_epilogue.h).

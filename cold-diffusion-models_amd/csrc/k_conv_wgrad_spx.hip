@@ -24,7 +24,8 @@ __device__ __forceinline__ void cdf_bf16x8_accum(float* acc8, const u32x4_v& h, 
 // consecutive pixels of one channel per lane) comes out of two ds_read_b64_tr_b16 -- gfx950's transposing LDS
 // read: the 16 lanes of a group hand in the addresses of a [4 px][16 ch] block (lane t: pixel t>>2, channels
 // 4(t&3)..+3) and lane t receives channel t's 4 pixels.  Pitch T+32 puts the 4 pixel rows of a group 16 banks
-// apart and the second group of the 32-lane pass 8 banks further: conflict-free.
+// apart and the second group of the 32-lane pass 8 banks further: conflict-free.  (That is the 32 x 32 x 16 geometry; on 16 x 16 x 32 a lane
+// holds 8 pixels of the 32-pixel chunk and the image is swizzled: cdf_px_off, cdf_conv_sp.h.)
 
 template <int T>
 struct SpxWgradSlot {                  // one operand's share of a thread's loads for a 32-pixel chunk
@@ -34,10 +35,30 @@ struct SpxWgradSlot {                  // one operand's share of a thread's load
     static constexpr int PITCH = T + 32;
 };
 
+// MFMA shape of the K loops below, per kernel form (32 = v_mfma_f32_32x32x16_bf16, 16 = v_mfma_f32_16x16x32_bf16; cdf_conv_sp.h), chosen like
+// cdf_halo_mfma (k_conv_halo.hip): a form is on 16 where that measured faster per launch and keeps its waves per SIMD, and has no instance of
+// the other shape.  Schedule, staging, split ranges and stores are the same in both; a 32-pixel chunk is ONE K step of the 16 shape (4 MFMAs
+// per 32 x 32 block and term) instead of two k16 steps of one, so the fragments of a whole chunk are live at once.
+constexpr int cdf_wgrad_spx_mfma(int TA, int TB, bool STACK2, int NS) {
+    // MI355X, B = 64, 16 against 32 per launch (profiles/wgrad_mfma_shape_ab.txt): the 128 x 128 tile in split precision +4.4 ... +5.8 % on the
+    // seven 3 x 3 layers that reach it, and it is the only one that wins.  NS = 1: every tile within the parent's own spread (-0.6 ... +1.8 %).
+    // The stacked tile: +0.3 %.  128 x 64: 126 -> 138 VGPRs, past the 128 of four waves per SIMD.  64 x 64: +2.4 ... +3.1 % alone, but 0.4 ... 0.9 %
+    // slower at the step's own two launches (kernel trace).  64 x 128 unstacked: no 3 x 3 layer reaches it, not measured alone.
+    return TA == 128 && TB == 128 && !STACK2 && NS == 3 ? 16 : 32;
+}
+constexpr int cdf_wgrad_row3_mfma(int TA, int TB, int NS) {
+    // the tiles with one 32-channel block per wave along dY run two blocks per CU at <= 128 VGPRs; the whole-chunk fragments take them past that
+    // (128 x 64: 128 -> 153, 64 x 128: 126 -> 144 in split precision, 128 x 64: 120 -> 134 in bf16), i.e. to one block per CU: they stay on 32
+    if (TA == 128 && TB == 64) return 32;
+    if (TA == 64 && TB == 128 && NS == 3) return 32;
+    // 128 x 128: +9.3 ... +12.7 % per launch in split precision (deep layers most), +4.7 ... +10.0 % in bf16; 64 x 128 in bf16: +3.1 %
+    return 16;
+}
+
 // STACK2 (TA = 128 with CA <= 64): a 64-channel A operand would fill only half of the 128 MFMA rows, so the tile takes
 // TWO taps -- rows 0..63 = tap 2*blockIdx.y, rows 64..127 = tap 2*blockIdx.y + 1 (all-zero when past the last tap).  The B
 // rows are shared: valid when every tap reads B at the same offset (plain convolutions; checked by the host).
-template <int TA, int TB, bool STACK2 = false, int NS = 3>
+template <int TA, int TB, bool STACK2 = false, int NS = 3, int MF = cdf_wgrad_spx_mfma(TA, TB, STACK2, NS)>
 __global__ void __launch_bounds__(256, 2) conv_wgrad_spx_kernel(SpxWgradArgs a) {
     using SA = SpxWgradSlot<TA>;
     using SB = SpxWgradSlot<TB>;
@@ -107,28 +128,32 @@ __global__ void __launch_bounds__(256, 2) conv_wgrad_spx_kernel(SpxWgradArgs a) 
         unsigned short* st = smem + buf * STAGE;
 #pragma unroll
         for (int p = 0; p < SA::PASS; ++p) {
-            const int so = (tid / SA::VPR + SA::PPP * p) * SA::PITCH + (tid % SA::VPR) * 8;
+            const int so = cdf_px_off<MF>(tid / SA::VPR + SA::PPP * p, (tid % SA::VPR) * 8, SA::PITCH);
             *(u32x4_v*)(st + so) = rah[p];
             if constexpr (NS == 3) *(u32x4_v*)(st + PLANE_A + so) = ral[p];
         }
 #pragma unroll
         for (int p = 0; p < SB::PASS; ++p) {
-            const int so = (tid / SB::VPR + SB::PPP * p) * SB::PITCH + (tid % SB::VPR) * 8;
+            const int so = cdf_px_off<MF>(tid / SB::VPR + SB::PPP * p, (tid % SB::VPR) * 8, SB::PITCH);
             *(u32x4_v*)(st + 2 * PLANE_A + so) = rbh[p];
             if constexpr (NS == 3) *(u32x4_v*)(st + 2 * PLANE_A + PLANE_B + so) = rbl[p];
             if (do_bsum) cdf_bf16x8_accum<NS>(bs_acc[p], rbh[p], rbl[p]);     // here the loads have landed anyway
         }
     };
 
-    f32x16_t acc[MT][NT];
+    typename cdf_acc_of<MF>::type acc[MT][NT];
     cdf_acc_zero(acc);
 
     const int half = lane >> 5, l31 = lane & 31;
-    // transposing-read lane geometry: group g = lane >> 4 -> channel block 16 (g & 1), pixel block 8 (g >> 1)
+    // transposing-read lane geometry.  MF = 32: group g = lane >> 4 -> channel block 16 (g & 1), pixel block 8 (g >> 1) of the k16 step.
+    // MF = 16: group g -> pixel block 8 g of the chunk; the fragment index is the 16-channel half instead of the k16 step (rows 8 g + q and
+    // 8 g + 4 + q share bit 3: one offset per half, the second read 4 pitches further)
     const int t16 = lane & 15, g16 = lane >> 4;
-    const int tr_row = (g16 >> 1) * 8 + (t16 >> 2), tr_col = (g16 & 1) * 16 + (t16 & 3) * 4;
-    const int tra = tr_row * SA::PITCH + wm * (TA / 2) + tr_col;
-    const int trb = tr_row * SB::PITCH + wn * (TB / 2) + tr_col;
+    const int tr_row = (MF == 16 ? g16 : g16 >> 1) * 8 + (t16 >> 2), tr_col = (MF == 16 ? 0 : (g16 & 1) * 16) + (t16 & 3) * 4;
+    const int tra = cdf_px_off<MF>(tr_row, tr_col, SA::PITCH, wm * (TA / 2));
+    const int trb = cdf_px_off<MF>(tr_row, tr_col, SB::PITCH, wn * (TB / 2));
+    const int tra1 = cdf_px_off<MF>(tr_row, tr_col + 16, SA::PITCH, wm * (TA / 2));
+    const int trb1 = cdf_px_off<MF>(tr_row, tr_col + 16, SB::PITCH, wn * (TB / 2));
     if (niter > 0) {
         load_global(0);
         store_lds(0);
@@ -139,23 +164,35 @@ __global__ void __launch_bounds__(256, 2) conv_wgrad_spx_kernel(SpxWgradArgs a) 
         if (it + 1 < niter) load_global(it + 1);
         const unsigned short* sa = smem + buf * STAGE;
         const unsigned short* sb = sa + 2 * PLANE_A;
+        if constexpr (MF == 16) {
+            bf16x8_v ah[2][MT], al[2][MT], bh[2][NT], bl[2][NT];
 #pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            bf16x8_v ah[MT], al[MT], bh[NT], bl[NT];
+            for (int h = 0; h < 2; ++h) {
 #pragma unroll
-            for (int i = 0; i < MT; ++i) {
-                cdf_tr_frag<NS>(sa + tra + ks * 16 * SA::PITCH + i * 32, PLANE_A, SA::PITCH, ah[i], al[i]);
+                for (int i = 0; i < MT; ++i) cdf_tr_frag<NS>(sa + (h ? tra1 : tra) + i * 32, PLANE_A, SA::PITCH, ah[h][i], al[h][i]);
+#pragma unroll
+                for (int j = 0; j < NT; ++j) cdf_tr_frag<NS>(sb + (h ? trb1 : trb) + j * 32, PLANE_B, SB::PITCH, bh[h][j], bl[h][j]);
             }
+            cdf_mma_tile<NS, MT, NT>(acc, ah, al, bh, bl);
+        } else {
 #pragma unroll
-            for (int j = 0; j < NT; ++j) {
-                cdf_tr_frag<NS>(sb + trb + ks * 16 * SB::PITCH + j * 32, PLANE_B, SB::PITCH, bh[j], bl[j]);
-            }
+            for (int ks = 0; ks < 2; ++ks) {
+                bf16x8_v ah[MT], al[MT], bh[NT], bl[NT];
 #pragma unroll
-            for (int i = 0; i < MT; ++i)
+                for (int i = 0; i < MT; ++i) {
+                    cdf_tr_frag<NS>(sa + tra + ks * 16 * SA::PITCH + i * 32, PLANE_A, SA::PITCH, ah[i], al[i]);
+                }
 #pragma unroll
                 for (int j = 0; j < NT; ++j) {
-                    cdf_mma_sp<NS>(acc[i][j], ah[i], al[i], bh[j], bl[j]);
+                    cdf_tr_frag<NS>(sb + trb + ks * 16 * SB::PITCH + j * 32, PLANE_B, SB::PITCH, bh[j], bl[j]);
                 }
+#pragma unroll
+                for (int i = 0; i < MT; ++i)
+#pragma unroll
+                    for (int j = 0; j < NT; ++j) {
+                        cdf_mma_sp<NS>(acc[i][j], ah[i], al[i], bh[j], bl[j]);
+                    }
+            }
         }
         if (it + 1 < niter) store_lds(buf ^ 1);
         __syncthreads();
@@ -203,7 +240,7 @@ __global__ void __launch_bounds__(256, 2) conv_wgrad_spx_kernel(SpxWgradArgs a) 
 // accumulator sets), one block per CU; grid (tiles, 3 tap rows, splits) in the XCD-aware order of cdf_wgrad_block.
 // Split range, bias fold and slab store are this kernel's own, kept on a measurement: see cdf_wgrad.h.
 // ================================================================================================
-template <int TA, int TB, int NS = 3>
+template <int TA, int TB, int NS = 3, int MF = cdf_wgrad_row3_mfma(TA, TB, NS)>
 __global__ void __launch_bounds__(512, 1) conv_wgrad_row3_kernel(SpxWgradArgs a) {
     constexpr int BK = 32, NTHR = 512;
     constexpr int WA_ = TA / 32, WB_ = 8 / WA_, TNW = TB / WB_, NT = TNW / 32;
@@ -294,46 +331,86 @@ __global__ void __launch_bounds__(512, 1) conv_wgrad_row3_kernel(SpxWgradArgs a)
 #pragma unroll
         for (int p = 0; p < PASS_A; ++p) {
             if (a_r[p] < NRAP) {
-                const int so = a_r[p] * PITCH_A + (tid % VPR_A) * 8;
+                const int so = cdf_px_off<MF>(a_r[p], (tid % VPR_A) * 8, PITCH_A);
                 *(u32x4_v*)(st + so) = r.ah[p];
                 if constexpr (NS == 3) *(u32x4_v*)(st + PLANE_A + so) = r.al[p];
             }
         }
         if (b_lane) {
-            const int so = pb * PITCH_B + (tid % VPR_B) * 8;
+            const int so = cdf_px_off<MF>(pb, (tid % VPR_B) * 8, PITCH_B);
             *(u32x4_v*)(st + 2 * PLANE_A + so) = r.bh;
             if constexpr (NS == 3) *(u32x4_v*)(st + 2 * PLANE_A + PLANE_B + so) = r.bl;
             if (do_bsum) cdf_bf16x8_accum<NS>(bs_acc, r.bh, r.bl);
         }
     };
 
-    f32x16_t acc[3][NT];
+    typename cdf_acc_of<MF>::type acc[3][NT];
     cdf_acc_zero(acc);
 
     const int half = lane >> 5, l31 = lane & 31;
+    // transposing-read lane geometry (see conv_wgrad_spx_kernel): MF = 32: pixels 8 (g >> 1) .. of the k16 step, channels 16 (g & 1) ..;
+    // MF = 16: pixels 8 g .. of the chunk, and the fragment index is the 16-channel half
     const int t16 = lane & 15, g16 = lane >> 4;
-    const int tr_row = (g16 >> 1) * 8 + (t16 >> 2), tr_col = (g16 & 1) * 16 + (t16 & 3) * 4;
-    const int trb = tr_row * PITCH_B + wb * TNW + tr_col;
+    const int tr_row = (MF == 16 ? g16 : g16 >> 1) * 8 + (t16 >> 2), tr_col = (MF == 16 ? 0 : (g16 & 1) * 16) + (t16 & 3) * 4;
+    const int trb = cdf_px_off<MF>(tr_row, tr_col, PITCH_B, wb * TNW);
+    const int trb1 = cdf_px_off<MF>(tr_row, tr_col + 16, PITCH_B, wb * TNW);   // (MF = 16: rows tr_row and tr_row + 4 share bit 3)
     // halo row of chunk pixel p for tap dx: p + 1 + dx (+ 2 from the second image row of a 16-wide chunk on)
+    // (MF = 32 only, whose image is plain: cdf_px_off<32> written out -- through the function the 128 x 64 tile compiles to 129 VGPRs instead of
+    //  128 and loses its second block per CU; the MF = 16 offsets are tra16 below)
     int tra[3];
 #pragma unroll
     for (int i = 0; i < 3; ++i) tra[i] = (tr_row + 1 + (int)a.dax[3 * grp + i]) * PITCH_A + wa * 32 + tr_col;
     const int ks_skip = W < 32 ? 2 * PITCH_A : 0;              // k-step 1 = pixels 16..31 = the second row when W = 16
 
     auto mma_ks = [&](const unsigned short* sa, const unsigned short* sb, int ks) {
-        bf16x8_v bh[NT], bl[NT];
-#pragma unroll
-        for (int j = 0; j < NT; ++j) {
-            cdf_tr_frag<NS>(sb + trb + ks * 16 * PITCH_B + j * 32, PLANE_B, PITCH_B, bh[j], bl[j]);
-        }
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            bf16x8_v ah, al;
-            cdf_tr_frag<NS>(sa + tra[i] + ks * (16 * PITCH_A + ks_skip), PLANE_A, PITCH_A, ah, al);
+        if constexpr (MF == 32) {
+            bf16x8_v bh[NT], bl[NT];
 #pragma unroll
             for (int j = 0; j < NT; ++j) {
-                cdf_mma_sp<NS>(acc[i][j], ah, al, bh[j], bl[j]);
+                cdf_tr_frag<NS>(sb + trb + ks * 16 * PITCH_B + j * 32, PLANE_B, PITCH_B, bh[j], bl[j]);
             }
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+                bf16x8_v ah, al;
+                cdf_tr_frag<NS>(sa + tra[i] + ks * (16 * PITCH_A + ks_skip), PLANE_A, PITCH_A, ah, al);
+#pragma unroll
+                for (int j = 0; j < NT; ++j) {
+                    cdf_mma_sp<NS>(acc[i][j], ah, al, bh[j], bl[j]);
+                }
+            }
+        }
+    };
+    // MF = 16: the chunk is one K step.  Groups 2 and 3 hold pixels 16 .. 31: the second image row when W = 16, two halo rows further on.  The X
+    // rows of a fragment, r and r + 4 with r = pixel + 1 + dx (+ 2), can differ in bit 3: an offset of its own for each (tap, read, half).
+    int tra16[3][2][2];
+    if constexpr (MF == 16) {
+        const int skip = (W < 32 && g16 >= 2) ? 2 : 0;
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int q = 0; q < 2; ++q)
+#pragma unroll
+                for (int h = 0; h < 2; ++h)
+                    tra16[i][q][h] = cdf_px_off<MF>(tr_row + 4 * q + 1 + (int)a.dax[3 * grp + i] + skip, tr_col + 16 * h, PITCH_A, wa * 32);
+    }
+    // the dY fragments of the chunk, tap 0, `mid` (the staging traffic the two k16 steps of the 32 shape have between them), taps 1 and 2
+    auto mma_chunk16 = [&](const unsigned short* sa, const unsigned short* sb, auto&& mid) {
+        if constexpr (MF == 16) {
+            bf16x8_v bh[2][NT], bl[2][NT];
+#pragma unroll
+            for (int h = 0; h < 2; ++h)
+#pragma unroll
+                for (int j = 0; j < NT; ++j) cdf_tr_frag<NS>(sb + (h ? trb1 : trb) + j * 32, PLANE_B, PITCH_B, bh[h][j], bl[h][j]);
+            auto tap = [&](int i) {
+                bf16x8_v ah[2][1], al[2][1];
+#pragma unroll
+                for (int h = 0; h < 2; ++h) cdf_tr_frag2<NS>(sa + tra16[i][0][h], sa + tra16[i][1][h], PLANE_A, ah[h][0], al[h][0]);
+                cdf_mma_tile<NS, 1, NT>(*reinterpret_cast<f32x4q_t(*)[1][NT]>(&acc[i]), ah, al, bh, bl);   // (tap i's row of blocks as a 1 x NT tile)
+            };
+            tap(0);
+            mid();
+            tap(1);
+            tap(2);
         }
     };
     if constexpr (X2) {
@@ -341,10 +418,17 @@ __global__ void __launch_bounds__(512, 1) conv_wgrad_row3_kernel(SpxWgradArgs a)
         auto step = [&](int it, Regs& nxt) {
             const unsigned short* sa = smem + (it & 1) * STAGE;
             const unsigned short* sb = sa + 2 * PLANE_A;
-            mma_ks(sa, sb, 0);
-            if (it + 1 < niter) store_lds(nxt, (it + 1) & 1);    // (that stage was last read in chunk it - 1: every wave is past the barrier that ended it)
-            if (it + 3 < niter) load_global(nxt, it + 3);
-            mma_ks(sa, sb, 1);
+            auto mid = [&]() {
+                if (it + 1 < niter) store_lds(nxt, (it + 1) & 1);    // (that stage was last read in chunk it - 1: every wave is past the barrier that ended it)
+                if (it + 3 < niter) load_global(nxt, it + 3);
+            };
+            if constexpr (MF == 16) {
+                mma_chunk16(sa, sb, mid);
+            } else {
+                mma_ks(sa, sb, 0);
+                mid();
+                mma_ks(sa, sb, 1);
+            }
             CDF_LDS_BARRIER();                                   // (LDS traffic only: the chunks in flight stay in flight)
         };
         if (niter > 0) {
@@ -368,8 +452,12 @@ __global__ void __launch_bounds__(512, 1) conv_wgrad_row3_kernel(SpxWgradArgs a)
             if (it + 1 < niter) load_global(r0, it + 1);
             const unsigned short* sa = smem + (it & 1) * STAGE;
             const unsigned short* sb = sa + 2 * PLANE_A;
-            mma_ks(sa, sb, 0);
-            mma_ks(sa, sb, 1);
+            if constexpr (MF == 16) {
+                mma_chunk16(sa, sb, []() {});
+            } else {
+                mma_ks(sa, sb, 0);
+                mma_ks(sa, sb, 1);
+            }
             if (it + 1 < niter) store_lds(r0, (it + 1) & 1);
             __syncthreads();
         }
