@@ -36,6 +36,12 @@ class TwoPhase:
     def fusable(self):
         return getattr(self, 'train_routine', 'Final') == 'Final'
 
+    def graph_safe(self):
+        """True only where prepare() (the draw of t and q_sample) never reads a device value on the host and takes nothing else from
+        the host that changes from step to step: then the Trainer may capture the step into a graph.  A core that was not checked
+        says False."""
+        return False
+
     def _draw_t(self, x):
         b, c, h, w = x.shape
         assert h == self.image_size and w == self.image_size, f'height and width of image must be {self.image_size}'
@@ -400,6 +406,10 @@ class DeblurDiffusion(TwoPhase, nn.Module):
         prefetch overlap with anything -- the per-step fallback reads max(t) on the host and would block the launching thread."""
         return self._uniform() and D.blur_fits_lds(self.image_size, self.image_size, self.gaussian_kernels[0].weight.shape[-1])
 
+    def graph_safe(self):
+        """Exactly when q_sample is the one fused launch: t is a device draw and the per-step fallback's int(torch.max(t)) is not reached."""
+        return self.can_prepare_async()
+
 
 # ===================================================================================================
 # denoising ("hot" Gaussian-noise baseline with cold-style samplers)
@@ -436,6 +446,10 @@ class DenoiseDiffusion(TwoPhase, nn.Module):
     def q_sample(self, x_start, x_end, t):
         ca, cb = self._tables()
         return D.noise_qsample(rt.check(x_start), x_end, ca, cb, t.contiguous())
+
+    def graph_safe(self):
+        """t is a device draw; q_sample is one launch that gathers the schedule tables (buffers) by t on the device."""
+        return True
 
     def get_x2_bar_from_xt(self, x1_bar, xt, t):
         ca, cb = self._tables()

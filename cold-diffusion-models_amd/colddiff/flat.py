@@ -61,10 +61,23 @@ class FusedAdam:
         self.exp_avg_sq = torch.zeros_like(self.arena.data)
         self.step_count = 0
         self.param_groups = [{"lr": lr, "betas": betas, "eps": eps, "params": self.arena.params}]
+        # graph mode only (Trainer(graph=True)): the step's scalars live in this device buffer (StepTable.hp) and step() neither counts
+        # nor bumps the weights epoch -- whoever uploads the scalars does, once per real step (a capture pass is not a step)
+        self.hp_dev = None
+
+    def host_params(self, step):
+        """The six scalars cdf_adam_step computes for `step` with the group's current lr / betas / eps, as 8 floats on the host."""
+        g = self.param_groups[0]
+        out = torch.empty(8, dtype=torch.float32)
+        rt.lib().cdf_adam_params(g["lr"], g["betas"][0], g["betas"][1], g["eps"], step, out.data_ptr())
+        return out
 
     def step(self):
         a = self.arena
         assert a.intact(), "parameters were moved after the optimizer was built (call .cuda() before creating the Trainer)"
+        if self.hp_dev is not None:
+            rt.lib().cdf_adam_step_dev(P(a.data), P(a.grad), P(self.exp_avg), P(self.exp_avg_sq), a.numel, P(self.hp_dev), rt.stream(a.data))
+            return
         self.step_count += 1
         g = self.param_groups[0]
         rt.lib().cdf_adam_step(P(a.data), P(a.grad), P(self.exp_avg), P(self.exp_avg_sq), a.numel, g["lr"], g["betas"][0], g["betas"][1],
@@ -81,6 +94,67 @@ class FusedAdam:
         self.step_count = sd["step"]
         self.exp_avg.copy_(sd["exp_avg"])
         self.exp_avg_sq.copy_(sd["exp_avg_sq"])
+
+
+class StepTable:
+    """The per-step host values of a graph-mode optimizer step in ONE static device buffer of 64-bit words:
+    [Adam's scalars: 4 words = 8 floats | loader indices: n_idx | dropout seeds: up to MAX_SEEDS].  A captured graph has the
+    buffer's addresses baked in; `upload` rewrites its contents before every step with one pinned, non-blocking copy (stream order
+    puts it behind the previous step's kernels, the caching host allocator keeps the staging block alive until the copy ran).
+
+    Dropout seeds: the blocks `take()` one slot each, in call order (the backward reuses its forward's slot).  How many a step takes is
+    not declared anywhere, so the first step after `reset_seeds()` runs in draw mode: take() draws the seed on the host as the eager
+    block does and writes it into its slot at once; the count is known from then on and `upload` carries that many seeds, drawn from
+    the same generator in the same order and number."""
+    MAX_SEEDS = 1024
+
+    def __init__(self, device, n_idx):
+        self.n_idx = n_idx
+        self.dev = torch.zeros(4 + n_idx + self.MAX_SEEDS, dtype=torch.int64, device=device)
+        self.hp = self.dev[:4].view(torch.float32)
+        self.idx = self.dev[4:4 + n_idx]
+        self.seeds = self.dev[4 + n_idx:]
+        assert self.hp.data_ptr() % 16 == 0
+        self.n_seeds = None          # None: not counted yet (draw mode)
+        self.taken = 0
+
+    def reset_seeds(self):
+        self.n_seeds, self.taken = None, 0
+
+    def upload(self, hp, idx, draw_seed):
+        n = 4 + self.n_idx + (self.n_seeds or 0)
+        host = torch.empty(n, dtype=torch.int64, pin_memory=True)
+        host[:4].view(torch.float32).copy_(hp)
+        if self.n_idx:
+            host[4:4 + self.n_idx].copy_(idx)
+        if self.n_seeds:
+            host[4 + self.n_idx:].copy_(torch.tensor([draw_seed() for _ in range(self.n_seeds)], dtype=torch.int64))
+        self.dev[:n].copy_(host, non_blocking=True)
+        self.taken = 0
+        self._draw = draw_seed if self.n_seeds is None else None
+
+    def rewind(self):
+        """Before a capture pass: the slots are handed out again from the first one, and nothing is drawn or written."""
+        assert self.n_seeds is not None
+        self.taken, self._draw = 0, None
+
+    def take(self):
+        k = self.taken
+        assert k < self.MAX_SEEDS, "more dropout layers than StepTable.MAX_SEEDS"
+        self.taken = k + 1
+        slot = self.seeds[k:k + 1]
+        if self._draw is not None:
+            slot.copy_(torch.tensor([self._draw()], dtype=torch.int64))
+        else:
+            assert k < self.n_seeds, "this step takes more dropout seeds than the step that was counted"
+        return slot
+
+    def end_step(self):
+        """After a step's forward: fix the count (draw mode) or check it."""
+        if self.n_seeds is None:
+            self.n_seeds = self.taken
+        assert self.taken == self.n_seeds, f"{self.taken} dropout seeds taken, {self.n_seeds} uploaded"
+        self._draw = None
 
 
 def ema_update(ema_arena, model_arena, beta):

@@ -654,6 +654,11 @@ def _seed():
     return int(torch.randint(0, 2 ** 62, (1,)).item())
 
 
+# Graph mode only (set by Trainer around its graph-form step, None otherwise): the flat.StepTable whose slots stand in for the host
+# seeds -- a block takes the next slot (a one-element int64 device tensor) and the kernels read the seed there.
+seed_table = None
+
+
 class GroupNormFn(torch.autograd.Function):
     """Normalize(C) [+ swish] as a standalone node (norm_out -> nonlinearity, Model2.py:329-330)."""
 
@@ -745,7 +750,7 @@ class ResnetBlockFn(torch.autograd.Function):
             (h1, mean1, rstd1), h1_s = ops.groupnorm_fwd(x, m.norm1.weight, m.norm1.bias, GN_GROUPS, GN_EPS, True), None
         h2 = conv_forward(h1, cin, m.conv1.weight, m.conv1.bias, sbias=tbias, xs=h1_s)
         p = m.dropout.p if m.training else 0.0
-        seed = _seed() if p > 0 else 0
+        seed = (_seed() if seed_table is None else seed_table.take()) if p > 0 else 0
         drop = (p, seed) if p > 0 else None
         if sp2:
             h3, mean2, rstd2, h3_s = ops.groupnorm_fwd(h2, m.norm2.weight, m.norm2.bias, GN_GROUPS, GN_EPS, True, split_out=True, planes_only=lean,

@@ -918,8 +918,12 @@ def groupnorm_fwd(x, gamma, beta, groups, eps, silu, split_out=False, planes_onl
     ws = torch.empty((B * nch * 2 * C,), device=x.device, dtype=torch.float32)
     ys = split_planes_like(x, B, H, W, C) if split_out else None
     p, seed = drop if drop is not None else (0.0, 0)
-    L.cdf_groupnorm_fwd_ex(P(x), ld_of(x), P(y), C, P(gamma), P(beta), P(mean), P(rstd), P(ws), B, HW, C, groups, eps, 1 if silu else 0,
-                           float(p), int(seed), P(ys[0]) if ys else 0, P(ys[1]) if ys else 0, ys[0].shape[-1] if ys else 0, rt.stream(x))
+    if torch.is_tensor(seed):                                # graph mode: the seed is a slot of the Trainer's device seed table
+        fn, seed = L.cdf_groupnorm_fwd_ex_sd, seed_ptr(seed, x)
+    else:
+        fn, seed = L.cdf_groupnorm_fwd_ex, int(seed)
+    fn(P(x), ld_of(x), P(y), C, P(gamma), P(beta), P(mean), P(rstd), P(ws), B, HW, C, groups, eps, 1 if silu else 0,
+       float(p), seed, P(ys[0]) if ys else 0, P(ys[1]) if ys else 0, ys[0].shape[-1] if ys else 0, rt.stream(x))
     if split_out:
         return y, mean, rstd, ys
     return y, mean, rstd
@@ -936,8 +940,12 @@ def groupnorm_bwd(dy, x, gamma_p, beta_p, mean, rstd, groups, silu, dx=None, dro
         dx = torch.empty((B, H, W, C), device=x.device, dtype=torch.float32)
     ws = torch.empty((B * nch * 2 * C + B * 2 * C + B * groups * 2,), device=x.device, dtype=torch.float32)
     p, seed = drop if drop is not None else (0.0, 0)
-    L.cdf_groupnorm_bwd_ex(P(dy), ld_of(dy), P(x), ld_of(x), P(gamma_p), P(beta_p), P(mean), P(rstd), P(dx), ld_of(dx),
-                           P(grad_of(gamma_p)), P(grad_of(beta_p)), P(ws), B, HW, C, groups, 1 if silu else 0, acc, 1, float(p), int(seed), rt.stream(x))
+    if torch.is_tensor(seed):
+        fn, seed = L.cdf_groupnorm_bwd_ex_sd, seed_ptr(seed, x)
+    else:
+        fn, seed = L.cdf_groupnorm_bwd_ex, int(seed)
+    fn(P(dy), ld_of(dy), P(x), ld_of(x), P(gamma_p), P(beta_p), P(mean), P(rstd), P(dx), ld_of(dx),
+       P(grad_of(gamma_p)), P(grad_of(beta_p)), P(ws), B, HW, C, groups, 1 if silu else 0, acc, 1, float(p), seed, rt.stream(x))
     return dx
 
 
@@ -1002,10 +1010,20 @@ def upsample2_bwd(dy, dx=None):
     return dx
 
 
+def seed_ptr(seed, like):
+    """Address of a dropout seed kept in device memory: one int64 element on `like`'s device (a slot of flat.SeedTable)."""
+    assert seed.dtype == torch.int64 and seed.numel() == 1 and seed.device == like.device, "a device seed is one int64 element next to the data"
+    return P(seed)
+
+
 def dropout(x, p, seed):
+    """seed: a Python int, or a one-element int64 device tensor (cdf_dropout_sd reads the word on the device)"""
     y = torch.empty(x.shape, device=x.device, dtype=torch.float32)
     rows = x.numel() // x.shape[-1]
-    rt.lib().cdf_dropout(P(x), ld_of(x), P(y), x.shape[-1], rows, x.shape[-1], p, seed, rt.stream(x))
+    if torch.is_tensor(seed):
+        rt.lib().cdf_dropout_sd(P(x), ld_of(x), P(y), x.shape[-1], rows, x.shape[-1], p, seed_ptr(seed, x), rt.stream(x))
+    else:
+        rt.lib().cdf_dropout(P(x), ld_of(x), P(y), x.shape[-1], rows, x.shape[-1], p, seed, rt.stream(x))
     return y
 
 

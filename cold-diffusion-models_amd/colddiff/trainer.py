@@ -242,9 +242,15 @@ class Trainer(EvalMixin):
     def __init__(self, diffusion_model, folder, *, ema_decay=0.995, image_size=128, train_batch_size=32, train_lr=2e-5,
                  train_num_steps=100000, gradient_accumulate_every=2, fp16=False, step_start_ema=2000, update_ema_every=10,
                  save_and_sample_every=1000, results_folder='./results', load_path=None, dataset=None, shuffle=True,
-                 num_workers=8, device_data=None):
+                 num_workers=8, device_data=None, graph=None):
         super().__init__()
         assert not fp16, "apex fp16 is not supported (every reference script passes fp16=False)"
+        # graph: replay the optimizer step as one captured graph where the Trainer is eligible (`_graph_reason`).  None = read
+        # COLDDIFF_GRAPH ("1" turns it on).  Off by default; decided at the first train_step / graph_state call.
+        if graph is None:
+            graph = os.environ.get("COLDDIFF_GRAPH") == "1"
+        self._graph_req = bool(graph)
+        self._gs = None
         self.model = diffusion_model
         self.ema = EMA(ema_decay)
         self.ema_model = copy.deepcopy(self.model)
@@ -359,6 +365,8 @@ class Trainer(EvalMixin):
         self.model.load_state_dict(_match_module_prefix(ckpt['model'], self.model.state_dict().keys()))
         self.ema_model.load_state_dict(_match_module_prefix(ckpt['ema'], self.ema_model.state_dict().keys()))
         rt.bump_weights_epoch()
+        if self._gs is not None:
+            self._graph_rewarm()
 
     # -- the hot loop (DEBLUR:1183-1235) -----------------------------------------------------------------
     def _next_batch(self):
@@ -504,6 +512,10 @@ class Trainer(EvalMixin):
     def train_step(self):
         """One optimizer step = gradient_accumulate_every micro-batches (one fused pass when `_can_fuse()`, else one forward /
         backward each: DEBLUR:1188-1195) + Adam (+ EMA); returns the mean micro-batch loss as a 0-dim device tensor (no host sync)."""
+        if self._graph_req:
+            loss = self._graph_train_step()
+            if loss is not None:
+                return loss
         acc = self.gradient_accumulate_every
         scale = 1.0 / (acc * parallel.world_size())
         total = None
@@ -530,6 +542,201 @@ class Trainer(EvalMixin):
         if self.step % self.update_ema_every == 0:
             self.step_ema()
         return total / acc
+
+    # -- graph mode: the optimizer step replayed as ONE captured graph (opt-in: Trainer(graph=True) / COLDDIFF_GRAPH=1) -------------
+    # The 32 x 32 configurations are host-bound: ~700 launches in ~10 ms of device time.  A replayed graph has no launch cost, but it
+    # re-runs its kernels with the arguments of the capture pass, so everything a step takes from the host lives in device memory
+    # (flat.StepTable: Adam's scalars, the loader's indices, the dropout seeds) and the host part of a step is one small upload:
+    #   upload -> [graph-form step: eagerly for the first GRAPH_WARMUP steps, captured once, replayed from then on] -> count, EMA
+    # The graph-form step is the fused / single micro-batch step without the side-stream prefetch (one chain of kernels), with
+    # cdf_adam_step_dev and the `_sd` dropout entry points; it advances NO host state, so the capture pass (which launches nothing) is
+    # not a step and the first replay is the next real step.  The trajectory is bit-identical to the eager Trainer's.
+    GRAPH_WARMUP = 3             # eager graph-form steps before a capture: lazily built caches (packed weights, their table, kernel stacks) settle in two
+
+    def graph_state(self):
+        """{'mode': 'off' | 'eager' | 'graph', 'reason', 'captures', 'replays'}: 'eager' = graph mode was requested and this Trainer
+        runs the ordinary step, for `reason`.  `captures` counts the graphs this Trainer set out to capture (the first one, and one
+        per change of something baked into the graph or load(): each warms up again); `replays` the steps a graph ran."""
+        gs = self._graph_decide()
+        return {k: gs[k] for k in ('mode', 'reason', 'captures', 'replays')}
+
+    def _graph_reason(self):
+        """Why the step cannot be captured (the first failed condition), None when it can: declared properties only."""
+        if self.device.type != 'cuda':
+            return "no HIP device"
+        if self.sync is not None:
+            return "more than one rank"
+        if rt._lib_override is not None:
+            return "library override"
+        if '_loss' in self.__dict__ or type(self)._loss is not Trainer._loss:
+            return "_loss is replaced"
+        if 'train_step' in self.__dict__ or type(self).train_step is not Trainer.train_step:
+            return "train_step is replaced"
+        if type(self)._second is not Trainer._second or type(self)._next_batch is not Trainer._next_batch:
+            return "_second / _next_batch is replaced"
+        if not (self._can_fuse() or self.gradient_accumulate_every == 1):
+            return "gradient accumulation does not fuse (_can_fuse)"
+        core = self.core
+        if not (hasattr(core, 'prepare') and hasattr(core, 'loss_prepared')):
+            return "the core has no two-phase form (prepare / loss_prepared)"
+        if not (hasattr(core, 'graph_safe') and core.graph_safe()):
+            return "the core's prepare is not graph_safe(): it may read device values on the host"
+        if isinstance(self.dl, DeviceLoader):
+            if self.dl.rrc:
+                return "the random_aug loader draws its parameters on the host"
+            if not self.dl.drop_last:
+                return "the loader keeps the short last batch (no drop_last)"
+        elif not isinstance(self.dl, SyntheticImages):
+            return "host DataLoader"
+        return None
+
+    def _graph_sig(self):
+        """What a captured step has baked in besides addresses; a change warms up and captures again.  (The learning rate is not
+        in it: it travels in the uploaded scalars.)"""
+        net = self.core._network() if hasattr(self.core, '_network') else self.core
+        return (rt.precision, self.batch_size, self.gradient_accumulate_every, self._fuse_off, self.core.training, net.training,
+                self.data_image_size, self.image_size, id(self.dl))
+
+    def _graph_set_mode(self, mode, reason):
+        self._gs['mode'], self._gs['reason'] = mode, reason
+        print(f"graph mode: {mode} ({reason})")
+
+    def _graph_decide(self):
+        if self._gs is None:
+            self._gs = {'mode': 'off', 'reason': 'not requested', 'captures': 0, 'replays': 0, 'graph': None, 'loss': None, 'warm': 0,
+                        'sig': None, 'table': None, 'keep': None}
+            if self._graph_req:
+                why = self._graph_reason()
+                self._graph_set_mode('eager' if why else 'graph', why or 'the step is captured after %d warm-up steps' % self.GRAPH_WARMUP)
+                if why is None:
+                    self._gs['captures'], self._gs['sig'] = 1, self._graph_sig()
+        return self._gs
+
+    def _graph_rewarm(self):
+        """Drop the graph and its static buffers; the next GRAPH_WARMUP steps are eager graph-form steps again."""
+        gs = self._gs
+        if gs['mode'] == 'graph':
+            gs['graph'] = gs['loss'] = gs['table'] = gs['keep'] = None
+            gs['warm'] = 0
+            gs['captures'] += 1
+
+    def _graph_snapshot(self):
+        gen = getattr(self.dl, 'gen', None)
+        return {'cpu': torch.get_rng_state(), 'cuda': torch.cuda.get_rng_state(self.device), 'gen': None if gen is None else gen.get_state(),
+                'dl': {k: getattr(self.dl, k) for k in ('epoch', 'pos', 'order', 'order_host') if hasattr(self.dl, k)},
+                'step_count': self.opt.step_count, 'pending': None if self._pending_q is None else list(self._pending_q)}
+
+    def _graph_restore(self, snap):
+        torch.set_rng_state(snap['cpu'])
+        torch.cuda.set_rng_state(snap['cuda'], self.device)
+        if snap['gen'] is not None:
+            self.dl.gen.set_state(snap['gen'])
+        for k, v in snap['dl'].items():
+            setattr(self.dl, k, v)
+        self.opt.step_count, self._pending_q = snap['step_count'], snap['pending']
+
+    def _graph_upload(self, table):
+        """The host part of a graph-mode step: the loader moves on and hands over this step's indices, the dropout seeds are drawn,
+        Adam's scalars are computed for the coming step -- one non-blocking upload."""
+        from . import functions as Fn
+        idx = None
+        if isinstance(self.dl, DeviceLoader):
+            idx = torch.cat([self.dl.take_indices() for _ in range(self.gradient_accumulate_every)])
+        table.upload(self.opt.host_params(self.opt.step_count + 1), idx, Fn._seed)
+
+    def _graph_form_step(self, table):
+        """forward / backward / Adam / zero_grad of one optimizer step with every per-step value read from `table`; advances no host
+        state.  Same kernels on the same values as train_step's fused (or single micro-batch) path without the prefetch."""
+        from . import functions as Fn
+        acc, B = self.gradient_accumulate_every, self.batch_size
+        Fn.seed_table, self.opt.hp_dev = table, table.hp
+        try:
+            preps = []
+            for i in range(acc):
+                batch = self.dl.batch_of(table.idx[i * B:(i + 1) * B]) if isinstance(self.dl, DeviceLoader) else self._next_batch()
+                x2 = self._second(batch)
+                preps.append(self.core.prepare(batch) if x2 is None else self.core.prepare(batch, x2))
+            if acc > 1:
+                prep = tuple(torch.cat(parts) for parts in zip(*preps))
+                loss = torch.mean(self.core.loss_prepared(prep))
+                (loss * (1.0 / parallel.world_size())).backward()
+                total = loss.detach() * acc
+            else:
+                loss = torch.mean(self.core.loss_prepared(preps[0]))
+                (loss * (1.0 / (acc * parallel.world_size()))).backward()
+                total = loss.detach()
+            table.end_step()
+            self.opt.step()
+            self.opt.zero_grad()
+            return total / acc
+        finally:
+            Fn.seed_table, self.opt.hp_dev = None, None
+
+    def _graph_capture(self, table):
+        """-> (graph, its static loss).  Launches nothing; the loader's generator is registered with the graph (torch registers the
+        default one), so a replay advances their offsets as the eager draws would."""
+        g = torch.cuda.CUDAGraph()
+        gen = getattr(self.dl, 'gen', None)
+        if gen is not None:
+            g.register_generator_state(gen)
+        table.rewind()
+        with torch.cuda.graph(g):
+            loss = self._graph_form_step(table)
+        # The graph has the addresses of cached buffers baked in that the caches REPLACE, not rewrite, when another model steps or
+        # samples in between (ops._repack_all builds a new record table for another set of layouts and drops the old one; a layout
+        # packed in another arithmetic mode gets new planes): the graph keeps what it was captured with alive.  It writes the packed
+        # layouts itself at every replay before it reads them, so it stays consistent whatever the caches point to by then.
+        from . import ops
+        self._gs['keep'] = (ops._pack_tables.get(self.device), [e.out for e in ops._pack_cache.values()], getattr(self.core, '_taps_cache', None))
+        return g, loss
+
+    def _graph_train_step(self):
+        """One optimizer step in graph mode; None when this Trainer runs (or from now on has to run) the ordinary step."""
+        gs = self._graph_decide()
+        if gs['mode'] != 'graph':
+            return None
+        sig = self._graph_sig()
+        if sig != gs['sig']:
+            gs['sig'] = sig
+            self._graph_rewarm()
+            why = self._graph_reason()
+            if why is not None:
+                self._graph_set_mode('eager', why)
+                return None
+        if gs['table'] is None:
+            n_idx = self.batch_size * self.gradient_accumulate_every if isinstance(self.dl, DeviceLoader) else 0
+            gs['table'] = flat.StepTable(self.device, n_idx)
+        table = gs['table']
+        if gs['graph'] is None and gs['warm'] < self.GRAPH_WARMUP:
+            self._graph_upload(table)
+            loss = self._graph_form_step(table)
+            gs['warm'] += 1
+        else:
+            if gs['graph'] is None:
+                # the capture pass is not a step: the graph-form step advances nothing on the host (loader position and epoch, Adam's
+                # step count, the generators, _pending_q stay where they are).  A pass that raises may have: the state of before is
+                # put back and the ordinary step takes over for good, from this very step (a capture is never tried twice).
+                snap = self._graph_snapshot()
+                try:
+                    gs['graph'], gs['loss'] = self._graph_capture(table)
+                    err = None
+                except Exception as e:
+                    err = f"the capture raised {type(e).__name__}: {e}"
+                rt.bump_weights_epoch()          # the pass marked packed layouts as current without writing them
+                if err is not None:
+                    self._graph_restore(snap)
+                    gs['graph'] = gs['loss'] = gs['table'] = gs['keep'] = None
+                    self._graph_set_mode('eager', err)
+                    return None
+            self._graph_upload(table)
+            gs['graph'].replay()
+            gs['replays'] += 1
+            loss = gs['loss'].clone()
+        self.opt.step_count += 1
+        rt.bump_weights_epoch()
+        if self.step % self.update_ema_every == 0:
+            self.step_ema()
+        return loss
 
     def train(self):
         acc_loss = 0
@@ -882,6 +1089,24 @@ class DeviceLoader:
             self.pos += B
             return self.cache.batch_jitter(idx, self.last_params)
         self.pos += B
+        return self.batch_of(idx)
+
+    def take_indices(self):
+        """Graph mode (drop_last loaders, not 'rrc'): move on by one batch exactly as __next__ does -- a new permutation at an epoch's
+        end -- and return the batch's image indices on the HOST (int64 [batch_size]); the Trainer uploads them into a static
+        device buffer and `batch_of` reads them there."""
+        assert self.drop_last and not self.rrc
+        B = self.batch_size
+        left = 0 if self.order is None else self.order.numel() - self.pos
+        if left < B:
+            self._new_epoch()
+        idx = self.order_host[self.pos:self.pos + B]
+        self.pos += B
+        return idx
+
+    def batch_of(self, idx):
+        """The batch of images idx (int64 on the device): crop offsets and mirrors are device draws from the loader's generator."""
+        B = idx.numel()
         dev = self.cache.data.device
         sy, sx = self.cache.span()
         if self.random_crop and (sy > 1 or sx > 1):

@@ -432,6 +432,10 @@ __device__ __forceinline__ unsigned cdf_hash32(unsigned long long seed, unsigned
     z = z ^ (z >> 31);
     return (unsigned)(z >> 32);
 }
+// The seed argument of a dropout kernel: the word itself, or where it lives in device memory (the `_sd` entry points, which refuse
+// a null pointer on the host).
+__device__ __forceinline__ unsigned long long cdf_seed_word(unsigned long long seed) { return seed; }
+__device__ __forceinline__ unsigned long long cdf_seed_word(const unsigned long long* seed) { return *seed; }
 
 // exact (erf) GELU, matches torch.nn.GELU(approximate='none')
 // erf by Abramowitz & Stegun 7.1.26 (|error| <= 1.5e-7 absolute), branch-free, ~14 instructions; also hands back

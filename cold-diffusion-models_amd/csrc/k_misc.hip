@@ -87,8 +87,11 @@ __global__ void upsample2_bwd_kernel(const float* dy, int lddy, float* dx, int l
 }
 
 // counter-based dropout mask (cdf_hash32, cdf_common.h): keep iff hash(seed, index) >= p*2^32 ; y = x * keep / (1-p)
-__global__ void dropout_kernel(const float* x, int ldx, float* y, int ldy, long long rows, int C, float p,
-                               unsigned long long seed) {
+// Seed: the 64-bit word by value (cdf_dropout), or a pointer to it in device memory (cdf_dropout_sd: a captured graph replays
+// the launch with a new word behind the same address); cdf_seed_word reads it once per thread.
+template <class Seed>
+__global__ void dropout_kernel(const float* x, int ldx, float* y, int ldy, long long rows, int C, float p, Seed seed_arg) {
+    const unsigned long long seed = cdf_seed_word(seed_arg);
     const unsigned thr = (unsigned)((double)p * 4294967296.0);
     const float inv = 1.0f / (1.0f - p);
     CDF_EW_LOOP(i, rows * C) {
@@ -102,19 +105,28 @@ __global__ void dropout_kernel(const float* x, int ldx, float* y, int ldy, long 
 // torch.optim.Adam (amsgrad=False, weight_decay=0, maximize=False), single-tensor CPU op order:
 //   m = m + (g - m)*(1-b1) ; v = v*b2 + ((1-b2)*g)*g ; denom = sqrt(v)/bc2_sqrt + eps ;
 //   p = p + (-step_size * m) / denom             with step_size = lr / bc1
+__device__ __forceinline__ void adam_element(float* p, const float* g, float* m, float* v, long long i, float one_minus_b1, float b2,
+                                             float one_minus_b2, float neg_step_size, float bc2_sqrt, float eps) {
+    const float gi = g[i];
+    float mi = m[i], vi = v[i];
+    mi = mi + (gi - mi) * one_minus_b1;
+    vi = vi * b2;
+    vi = vi + (one_minus_b2 * gi) * gi;
+    const float denom = sqrtf(vi) / bc2_sqrt + eps;
+    p[i] = p[i] + (neg_step_size * mi) / denom;
+    m[i] = mi;
+    v[i] = vi;
+}
 __global__ void adam_kernel(float* p, const float* g, float* m, float* v, long long n, float one_minus_b1, float b2,
                             float one_minus_b2, float neg_step_size, float bc2_sqrt, float eps) {
-    CDF_EW_LOOP(i, n) {
-        const float gi = g[i];
-        float mi = m[i], vi = v[i];
-        mi = mi + (gi - mi) * one_minus_b1;
-        vi = vi * b2;
-        vi = vi + (one_minus_b2 * gi) * gi;
-        const float denom = sqrtf(vi) / bc2_sqrt + eps;
-        p[i] = p[i] + (neg_step_size * mi) / denom;
-        m[i] = mi;
-        v[i] = vi;
-    }
+    CDF_EW_LOOP(i, n) adam_element(p, g, m, v, i, one_minus_b1, b2, one_minus_b2, neg_step_size, bc2_sqrt, eps);
+}
+// the same step with its six scalars in device memory (hp[0..5] as cdf_adam_params lays them out, 16-byte aligned): a captured graph
+// replays this launch, and the host only rewrites hp between replays
+__global__ void adam_dev_kernel(float* p, const float* g, float* m, float* v, long long n, const float* hp) {
+    const float4 a = *(const float4*)hp;
+    const float2 b = *(const float2*)(hp + 4);
+    CDF_EW_LOOP(i, n) adam_element(p, g, m, v, i, a.x, a.y, a.z, a.w, b.x, b.y);
 }
 // EMA: ma = ma*beta + (1-beta)*p   (DEBLUR:78-81)
 __global__ void ema_kernel(float* ma, const float* p, long long n, float beta, float one_minus_beta) {
@@ -282,17 +294,48 @@ extern "C" int cdf_upsample2_bwd(const float* dy, int lddy, float* dx, int lddx,
 extern "C" int cdf_dropout(const float* x, int ldx, float* y, int ldy, long long rows, int C, float p,
                            long long seed, void* stream) {
     CDF_REQUIRE(x && y && rows > 0 && C > 0 && p >= 0.f && p < 1.f, "cdf_dropout: bad args");
-    CDF_LAUNCH(dropout_kernel, dim3(cdf_ew_grid8k(rows * C)), dim3(256), 0, CDF_S, x, ldx, y, ldy, rows, C, p, (unsigned long long)seed);
+    CDF_LAUNCH(dropout_kernel<unsigned long long>, dim3(cdf_ew_grid8k(rows * C)), dim3(256), 0, CDF_S, x, ldx, y, ldy, rows, C, p, (unsigned long long)seed);
     return cdf_check_launch("dropout");
+}
+extern "C" int cdf_dropout_sd(const float* x, int ldx, float* y, int ldy, long long rows, int C, float p,
+                              const long long* seed_dev, void* stream) {
+    CDF_REQUIRE(x && y && rows > 0 && C > 0 && p >= 0.f && p < 1.f, "cdf_dropout: bad args");
+    CDF_REQUIRE(seed_dev && ((uintptr_t)seed_dev & 7) == 0, "cdf_dropout_sd: seed_dev must be a non-null, 8B aligned device pointer");
+    CDF_LAUNCH(dropout_kernel<const unsigned long long*>, dim3(cdf_ew_grid8k(rows * C)), dim3(256), 0, CDF_S, x, ldx, y, ldy, rows, C, p,
+               (const unsigned long long*)seed_dev);
+    return cdf_check_launch("dropout_sd");
+}
+// the ONE statement of Adam's host arithmetic: double bias corrections, then one rounding to float each
+static void adam_params(double lr, double beta1, double beta2, double eps, int step, float out[8]) {
+    const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
+    const double step_size = lr / bc1;
+    out[0] = (float)(1.0 - beta1);
+    out[1] = (float)beta2;
+    out[2] = (float)(1.0 - beta2);
+    out[3] = (float)(-step_size);
+    out[4] = (float)sqrt(bc2);
+    out[5] = (float)eps;
+    out[6] = out[7] = 0.f;
+}
+extern "C" int cdf_adam_params(double lr, double beta1, double beta2, double eps, int step, float* out) {
+    CDF_REQUIRE(out && step >= 1, "cdf_adam_params: bad args");
+    adam_params(lr, beta1, beta2, eps, step, out);
+    return CDF_OK;
 }
 extern "C" int cdf_adam_step(float* p, const float* g, float* m, float* v, long long n, double lr, double beta1,
                              double beta2, double eps, int step, void* stream) {
     CDF_REQUIRE(p && g && m && v && n > 0 && step >= 1, "cdf_adam_step: bad args");
-    const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
-    const double step_size = lr / bc1;
-    CDF_LAUNCH(adam_kernel, dim3(cdf_ew_grid8k(n)), dim3(256), 0, CDF_S, p, g, m, v, n, (float)(1.0 - beta1), (float)beta2,
-               (float)(1.0 - beta2), (float)(-step_size), (float)sqrt(bc2), (float)eps);
+    float hp[8];
+    adam_params(lr, beta1, beta2, eps, step, hp);
+    CDF_LAUNCH(adam_kernel, dim3(cdf_ew_grid8k(n)), dim3(256), 0, CDF_S, p, g, m, v, n, hp[0], hp[1], hp[2], hp[3], hp[4], hp[5]);
     return cdf_check_launch("adam");
+}
+extern "C" int cdf_adam_step_dev(float* p, const float* g, float* m, float* v, long long n, const float* hp, void* stream) {
+    CDF_REQUIRE(p && g && m && v && n > 0, "cdf_adam_step_dev: bad args");
+    CDF_REQUIRE(hp, "cdf_adam_step_dev: null hp");
+    CDF_REQUIRE(((uintptr_t)hp & 15) == 0, "cdf_adam_step_dev: hp must be 16B aligned");
+    CDF_LAUNCH(adam_dev_kernel, dim3(cdf_ew_grid8k(n)), dim3(256), 0, CDF_S, p, g, m, v, n, hp);
+    return cdf_check_launch("adam_dev");
 }
 extern "C" int cdf_ema_update(float* ma, const float* p, long long n, double beta, void* stream) {
     CDF_REQUIRE(ma && p && n > 0, "cdf_ema_update: bad args");

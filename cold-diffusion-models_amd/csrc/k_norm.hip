@@ -252,10 +252,14 @@ __global__ void __launch_bounds__(1024) norm_param_reduce_kernel(const float* pa
 //   mode 0 (fwd stats) : p0 = sum x            p1 = sum x^2
 //   mode 1 (bwd)       : p0 = sum dz           p1 = sum dz * xhat,  dz = dy * act'(xhat*gamma+beta)
 // part layout [B][nchunk][2][C]; grid = (ceil(C/64), nchunk, B); block 256 = 4 row lanes x 64 ch
+// Seed (here and in the two apply kernels): the dropout seed by value, or a pointer to it in device memory (the `_sd` entry points;
+// cdf_seed_word, cdf_common.h) -- read once per thread.
+template <class Seed>
 __global__ void groupnorm_partial_kernel(const float* x, int ldx, const float* dy, int lddy, const float* gamma,
                                          const float* beta, const float* mean, const float* rstd, float* part, int HW,
                                          int rows_per_chunk, int C, int groups, int mode, int silu, float p_drop,
-                                         unsigned long long seed) {
+                                         Seed seed_arg) {
+    const unsigned long long seed = cdf_seed_word(seed_arg);
     // p_drop > 0 (mode 1): dy is the gradient of the DROPPED output, the mask (cdf_dropout's, element (b HW + r) C + c) is applied here
     const unsigned thr = (unsigned)((double)p_drop * 4294967296.0);
     const float inv = 1.0f / (1.0f - p_drop);
@@ -402,9 +406,11 @@ __global__ void __launch_bounds__(1024) groupnorm_bwd_param_kernel(const float* 
 // y = drop(act((x-mean)*rstd*gamma+beta)); float4 over channels.  Optional tail of the ResnetBlock chain (Model2.py:118-126): the
 // dropout mask of cdf_dropout (same hash, same element index) and the result again as bf16 hi / lo planes (the next conv's operand
 // split, bit-equal to cdf_split_bf16 of y); y may be null when only the planes are wanted.
+template <class Seed>
 __global__ void groupnorm_apply_kernel(const float* x, int ldx, float* y, int ldy, const float* gamma, const float* beta,
                                        const float* mean, const float* rstd, int B, int HW, int C, int groups, int silu, float p_drop,
-                                       unsigned long long seed, unsigned short* y_hi, unsigned short* y_lo, int ld_ys) {
+                                       Seed seed_arg, unsigned short* y_hi, unsigned short* y_lo, int ld_ys) {
+    const unsigned long long seed = cdf_seed_word(seed_arg);
     const int c4n = C / 4, cg = C / groups;
     const unsigned thr = (unsigned)((double)p_drop * 4294967296.0);
     const float inv = 1.0f / (1.0f - p_drop);
@@ -429,10 +435,12 @@ __global__ void groupnorm_apply_kernel(const float* x, int ldx, float* y, int ld
 }
 
 // dx = rstd * (dz*gamma - s1 - xhat*s2)
+template <class Seed>
 __global__ void groupnorm_bwd_apply_kernel(const float* dy, int lddy, const float* x, int ldx, const float* gamma,
                                            const float* beta, const float* mean, const float* rstd, const float* s12,
                                            float* dx, int lddx, int B, int HW, int C, int groups, int silu,
-                                           int accumulate, float p_drop, unsigned long long seed) {
+                                           int accumulate, float p_drop, Seed seed_arg) {
+    const unsigned long long seed = cdf_seed_word(seed_arg);
     const int c4n = C / 4, cg = C / groups;
     const unsigned thr = (unsigned)((double)p_drop * 4294967296.0);
     const float inv = 1.0f / (1.0f - p_drop);
@@ -590,24 +598,41 @@ extern "C" int cdf_groupnorm_nchunk(int HW) {
 }
 
 // ws: >= B * nchunk * 2 * C floats ; mean/rstd: [B][groups]
-extern "C" int cdf_groupnorm_fwd_ex(const float* x, int ldx, float* y, int ldy, const float* gamma, const float* beta,
-                                    float* mean, float* rstd, float* ws, int B, int HW, int C, int groups, float eps,
-                                    int silu, float p_drop, long long seed, void* y_hi, void* y_lo, int ld_ys, void* stream) {
+template <class Seed>
+static int groupnorm_fwd_ex(const float* x, int ldx, float* y, int ldy, const float* gamma, const float* beta,
+                            float* mean, float* rstd, float* ws, int B, int HW, int C, int groups, float eps,
+                            int silu, float p_drop, Seed seed, void* y_hi, void* y_lo, int ld_ys, void* stream) {
     CDF_REQUIRE(x && (y || y_hi) && gamma && beta && mean && rstd && ws, "cdf_groupnorm_fwd: null pointer");
     CDF_REQUIRE(C % groups == 0 && C % 4 == 0 && ldx % 4 == 0 && (!y || ldy % 4 == 0), "cdf_groupnorm_fwd: C=%d groups=%d", C, groups);
     CDF_REQUIRE(p_drop >= 0.f && p_drop < 1.f, "cdf_groupnorm_fwd: dropout probability %g", (double)p_drop);
     CDF_REQUIRE(!y_hi || (ld_ys % 4 == 0 && ld_ys >= C && ((((uintptr_t)y_hi) | ((uintptr_t)y_lo)) & 7) == 0), "cdf_groupnorm_fwd: bad output planes");
     CDF_REQUIRE(y_hi || !y_lo, "cdf_groupnorm_fwd: lo plane without hi plane");
     const int nchunk = cdf_groupnorm_nchunk(HW), rpc = cdf_cdiv(HW, nchunk);
-    CDF_LAUNCH(groupnorm_partial_kernel, dim3(cdf_cdiv(C, 64), nchunk, B), dim3(256), 0, CDF_S, x, ldx, (const float*)nullptr, 0,
+    CDF_LAUNCH(groupnorm_partial_kernel<unsigned long long>, dim3(cdf_cdiv(C, 64), nchunk, B), dim3(256), 0, CDF_S, x, ldx, (const float*)nullptr, 0,
                gamma, beta, (const float*)nullptr, (const float*)nullptr, ws, HW, rpc, C, groups, 0, 0, 0.f, 0ull);
     CDF_LAUNCH(groupnorm_stats_kernel, dim3(B), dim3(64), 0, CDF_S, (const float*)ws, nchunk, C, groups, HW, eps, mean, rstd);
     const long long n = (long long)B * HW * (C / 4);
     int grid = (int)((n + 255) / 256);
     if (grid > 4096) grid = 4096;
-    CDF_LAUNCH(groupnorm_apply_kernel, dim3(grid), dim3(256), 0, CDF_S, x, ldx, y, ldy, gamma, beta, (const float*)mean, (const float*)rstd, B, HW, C, groups, silu,
-               p_drop, (unsigned long long)seed, (unsigned short*)y_hi, (unsigned short*)y_lo, ld_ys);
+    CDF_LAUNCH(groupnorm_apply_kernel<Seed>, dim3(grid), dim3(256), 0, CDF_S, x, ldx, y, ldy, gamma, beta, (const float*)mean, (const float*)rstd, B, HW, C, groups, silu,
+               p_drop, seed, (unsigned short*)y_hi, (unsigned short*)y_lo, ld_ys);
     return cdf_check_launch("groupnorm_fwd");
+}
+extern "C" int cdf_groupnorm_fwd_ex(const float* x, int ldx, float* y, int ldy, const float* gamma, const float* beta,
+                                    float* mean, float* rstd, float* ws, int B, int HW, int C, int groups, float eps,
+                                    int silu, float p_drop, long long seed, void* y_hi, void* y_lo, int ld_ys, void* stream) {
+    return groupnorm_fwd_ex(x, ldx, y, ldy, gamma, beta, mean, rstd, ws, B, HW, C, groups, eps, silu, p_drop, (unsigned long long)seed, y_hi, y_lo,
+                            ld_ys, stream);
+}
+// the same with the seed in device memory: a captured graph replays these launches and the host rewrites the word between replays
+#define CDF_REQUIRE_SEED_DEV(name) \
+    CDF_REQUIRE(seed_dev && ((uintptr_t)seed_dev & 7) == 0, name ": seed_dev must be a non-null, 8B aligned device pointer")
+extern "C" int cdf_groupnorm_fwd_ex_sd(const float* x, int ldx, float* y, int ldy, const float* gamma, const float* beta,
+                                       float* mean, float* rstd, float* ws, int B, int HW, int C, int groups, float eps,
+                                       int silu, float p_drop, const long long* seed_dev, void* y_hi, void* y_lo, int ld_ys, void* stream) {
+    CDF_REQUIRE_SEED_DEV("cdf_groupnorm_fwd_ex_sd");
+    return groupnorm_fwd_ex(x, ldx, y, ldy, gamma, beta, mean, rstd, ws, B, HW, C, groups, eps, silu, p_drop, (const unsigned long long*)seed_dev,
+                            y_hi, y_lo, ld_ys, stream);
 }
 extern "C" int cdf_groupnorm_fwd(const float* x, int ldx, float* y, int ldy, const float* gamma, const float* beta,
                                  float* mean, float* rstd, float* ws, int B, int HW, int C, int groups, float eps,
@@ -617,10 +642,11 @@ extern "C" int cdf_groupnorm_fwd(const float* x, int ldx, float* y, int ldy, con
 }
 
 // ws: >= B*nchunk*2*C + B*2*C + B*groups*2 floats
-extern "C" int cdf_groupnorm_bwd_ex(const float* dy, int lddy, const float* x, int ldx, const float* gamma,
-                                    const float* beta, const float* mean, const float* rstd, float* dx, int lddx,
-                                    float* dgamma, float* dbeta, float* ws, int B, int HW, int C, int groups, int silu,
-                                    int accumulate_dx, int accumulate_param, float p_drop, long long seed, void* stream) {
+template <class Seed>
+static int groupnorm_bwd_ex(const float* dy, int lddy, const float* x, int ldx, const float* gamma,
+                            const float* beta, const float* mean, const float* rstd, float* dx, int lddx,
+                            float* dgamma, float* dbeta, float* ws, int B, int HW, int C, int groups, int silu,
+                            int accumulate_dx, int accumulate_param, float p_drop, Seed seed, void* stream) {
     CDF_REQUIRE(dy && x && gamma && beta && mean && rstd && dx && dgamma && dbeta && ws, "cdf_groupnorm_bwd: null pointer");
     CDF_REQUIRE(C % groups == 0 && C % 4 == 0 && ldx % 4 == 0 && lddy % 4 == 0 && lddx % 4 == 0, "cdf_groupnorm_bwd: bad C / pitch");
     CDF_REQUIRE(p_drop >= 0.f && p_drop < 1.f, "cdf_groupnorm_bwd: dropout probability %g", (double)p_drop);
@@ -628,17 +654,32 @@ extern "C" int cdf_groupnorm_bwd_ex(const float* dy, int lddy, const float* x, i
     float* part = ws;
     float* ab = part + (size_t)B * nchunk * 2 * C;
     float* s12 = ab + (size_t)B * 2 * C;
-    CDF_LAUNCH(groupnorm_partial_kernel, dim3(cdf_cdiv(C, 64), nchunk, B), dim3(256), 0, CDF_S, x, ldx, dy, lddy, gamma, beta, mean, rstd,
-               part, HW, rpc, C, groups, 1, silu, p_drop, (unsigned long long)seed);
+    CDF_LAUNCH(groupnorm_partial_kernel<Seed>, dim3(cdf_cdiv(C, 64), nchunk, B), dim3(256), 0, CDF_S, x, ldx, dy, lddy, gamma, beta, mean, rstd,
+               part, HW, rpc, C, groups, 1, silu, p_drop, seed);
     CDF_LAUNCH(groupnorm_bwd_reduce_kernel, dim3(cdf_cdiv(B * 2 * C, 256)), dim3(256), 0, CDF_S, (const float*)part, nchunk, B, C, ab);
     CDF_LAUNCH(groupnorm_bwd_group_kernel, dim3(cdf_cdiv(B * groups, 256)), dim3(256), 0, CDF_S, (const float*)ab, B, C, groups, HW, gamma, s12);
     CDF_LAUNCH(groupnorm_bwd_param_kernel, dim3(cdf_cdiv(C, 64)), dim3(1024), 0, CDF_S, (const float*)ab, B, C, dgamma, dbeta, accumulate_param);
     const long long n = (long long)B * HW * (C / 4);
     int grid = (int)((n + 255) / 256);
     if (grid > 4096) grid = 4096;
-    CDF_LAUNCH(groupnorm_bwd_apply_kernel, dim3(grid), dim3(256), 0, CDF_S, dy, lddy, x, ldx, gamma, beta, mean, rstd, (const float*)s12,
-               dx, lddx, B, HW, C, groups, silu, accumulate_dx, p_drop, (unsigned long long)seed);
+    CDF_LAUNCH(groupnorm_bwd_apply_kernel<Seed>, dim3(grid), dim3(256), 0, CDF_S, dy, lddy, x, ldx, gamma, beta, mean, rstd, (const float*)s12,
+               dx, lddx, B, HW, C, groups, silu, accumulate_dx, p_drop, seed);
     return cdf_check_launch("groupnorm_bwd");
+}
+extern "C" int cdf_groupnorm_bwd_ex(const float* dy, int lddy, const float* x, int ldx, const float* gamma,
+                                    const float* beta, const float* mean, const float* rstd, float* dx, int lddx,
+                                    float* dgamma, float* dbeta, float* ws, int B, int HW, int C, int groups, int silu,
+                                    int accumulate_dx, int accumulate_param, float p_drop, long long seed, void* stream) {
+    return groupnorm_bwd_ex(dy, lddy, x, ldx, gamma, beta, mean, rstd, dx, lddx, dgamma, dbeta, ws, B, HW, C, groups, silu, accumulate_dx,
+                            accumulate_param, p_drop, (unsigned long long)seed, stream);
+}
+extern "C" int cdf_groupnorm_bwd_ex_sd(const float* dy, int lddy, const float* x, int ldx, const float* gamma,
+                                       const float* beta, const float* mean, const float* rstd, float* dx, int lddx,
+                                       float* dgamma, float* dbeta, float* ws, int B, int HW, int C, int groups, int silu,
+                                       int accumulate_dx, int accumulate_param, float p_drop, const long long* seed_dev, void* stream) {
+    CDF_REQUIRE_SEED_DEV("cdf_groupnorm_bwd_ex_sd");
+    return groupnorm_bwd_ex(dy, lddy, x, ldx, gamma, beta, mean, rstd, dx, lddx, dgamma, dbeta, ws, B, HW, C, groups, silu, accumulate_dx,
+                            accumulate_param, p_drop, (const unsigned long long*)seed_dev, stream);
 }
 extern "C" int cdf_groupnorm_bwd(const float* dy, int lddy, const float* x, int ldx, const float* gamma,
                                  const float* beta, const float* mean, const float* rstd, float* dx, int lddx,

@@ -28,7 +28,7 @@ extern "C" {
 /* Bumped whenever an exported signature changes incompatibly (rounds 1-3 all answered 1 while arguments were added: `tiled`,
  * `onepass`, `slots`, `tune`).  cdf_abi_version() returns the value the LIBRARY was built with; a binding compares it with the
  * header it was generated from before the first call (colddiff/_lib.py does) -- a mismatched pair would read shifted arguments. */
-#define CDF_ABI_VERSION 15
+#define CDF_ABI_VERSION 16
 
 #define CDF_E_INVALID (-1)
 #define CDF_E_UNSUPPORTED (-2)
@@ -569,6 +569,16 @@ int cdf_groupnorm_bwd_ex(const float* dy, int lddy, const float* x, int ldx, con
 int cdf_groupnorm_fwd_ex(const float* x, int ldx, float* y, int ldy, const float* gamma, const float* beta, float* mean,
                          float* rstd, float* ws, int B, int HW, int C, int groups, float eps, int silu, float p_drop,
                          long long seed, void* y_hi, void* y_lo, int ld_ys, void* stream);
+/* the two above with the dropout seed in DEVICE memory (`seed_dev`: one 64-bit word, 8-byte aligned, never null; read once per thread):
+ * same hash, index and threshold, bit-identical results for the same word.  A captured graph replays these launches while the host
+ * rewrites the word between replays.  Argument checks and messages are those of the by-value entry points. */
+int cdf_groupnorm_bwd_ex_sd(const float* dy, int lddy, const float* x, int ldx, const float* gamma, const float* beta,
+                            const float* mean, const float* rstd, float* dx, int lddx, float* dgamma, float* dbeta, float* ws,
+                            int B, int HW, int C, int groups, int silu, int accumulate_dx, int accumulate_param, float p_drop,
+                            const long long* seed_dev, void* stream);
+int cdf_groupnorm_fwd_ex_sd(const float* x, int ldx, float* y, int ldy, const float* gamma, const float* beta, float* mean,
+                            float* rstd, float* ws, int B, int HW, int C, int groups, float eps, int silu, float p_drop,
+                            const long long* seed_dev, void* y_hi, void* y_lo, int ld_ys, void* stream);
 int cdf_groupnorm_bwd(const float* dy, int lddy, const float* x, int ldx, const float* gamma, const float* beta,
                       const float* mean, const float* rstd, float* dx, int lddx, float* dgamma, float* dbeta, float* ws,
                       int B, int HW, int C, int groups, int silu, int accumulate_dx, int accumulate_param,
@@ -697,9 +707,18 @@ int cdf_upsample2_bwd(const float* dy, int lddy, float* dx, int lddx, int B, int
 /* dropout with a counter-based mask (same seed => same mask, used again in backward) */
 int cdf_dropout(const float* x, int ldx, float* y, int ldy, long long rows, int C, float p, long long seed,
                 void* stream);
+/* cdf_dropout with the seed in device memory (see cdf_groupnorm_fwd_ex_sd) */
+int cdf_dropout_sd(const float* x, int ldx, float* y, int ldy, long long rows, int C, float p, const long long* seed_dev,
+                   void* stream);
 /* torch.optim.Adam defaults over a flat arena (DEBLUR:1117,1200); `step` is the 1-based step count */
 int cdf_adam_step(float* p, const float* g, float* m, float* v, long long n, double lr, double beta1, double beta2,
                   double eps, int step, void* stream);
+/* host only, no launch: the scalars cdf_adam_step hands its kernel for these arguments, with its double arithmetic and float roundings.
+ * out (8 floats, host memory) = 1 - beta1, beta2, 1 - beta2, -lr / bc1, sqrt(bc2), eps, 0, 0 */
+int cdf_adam_params(double lr, double beta1, double beta2, double eps, int step, float* out);
+/* cdf_adam_step with those scalars read from DEVICE memory `hp` (cdf_adam_params' layout, 16-byte aligned, checked on the host): the same
+ * element-wise arithmetic, bit-identical for the same scalars.  The step of a captured graph: the host rewrites hp between replays. */
+int cdf_adam_step_dev(float* p, const float* g, float* m, float* v, long long n, const float* hp, void* stream);
 /* EMA.update_average (DEBLUR:78-81): ma = ma*beta + (1-beta)*p */
 int cdf_ema_update(float* ma, const float* p, long long n, double beta, void* stream);
 int cdf_scale(float* x, long long n, float s, void* stream);
