@@ -672,7 +672,7 @@ class DecolorTrainer(Trainer):
                 Image.fromarray(np.concatenate(framed, axis=1)).save(str(self.results_folder / f'all_{cnt}.png'))
                 cnt += 1
 
-    def fid_distance_decrease_from_manifold(self, fid_func, start=0, end=1000, eval_batch_size=16, shard=False):
+    def fid_distance_decrease_from_manifold(self, fid_func, start=0, end=1000, eval_batch_size=16, shard=False, lpips=None):
         """Degrade -> restore the dataset items idx with start < idx <= end of a `np.random.permutation` walk (numpy's global stream, as
         upstream); RMSE / SSIM (/ FID when fid_func is given) of the degraded, the sampled and the directly reconstructed sets against
         the originals.  The items are the dataset's own (upstream does not pass them through `post_process_func`: with `to_lab` the
@@ -686,11 +686,14 @@ class DecolorTrainer(Trainer):
         `shard`: under `torch.distributed.run` with W > 1 ranks, rank r runs the batches k with k % W == r of rank 0's permutation (every
         rank still draws its own, so its numpy stream advances as without the keyword), the accumulators are all-reduced at the end, every
         rank returns the same dict and rank 0 prints (fid_func: None or one with `new_stats`).
+        `lpips`: a `metrics.DeviceLpips` adds `lpips_<name>` and one printed line per name, from the same four [-1, 1] sets per batch
+        (fid_func: None or one with `new_stats`).
         -> the numbers upstream prints."""
         import numpy as np
         import torch.nn.functional as F
         from . import metrics
-        from .evaluate import shard_ranks
+        from .evaluate import check_lpips_sweep, shard_ranks
+        check_lpips_sweep(lpips, fid_func)
         rank, world = shard_ranks(shard, fid_func)
         say = print if rank == 0 else (lambda *a, **kw: None)
         say(len(self.ds))
@@ -713,6 +716,7 @@ class DecolorTrainer(Trainer):
         names = ('blur', 'deblur', 'direct_deblur')
         stats = metrics.PairStats(names)
         fstats = [fid_func.new_stats() for _ in range(4)] if hasattr(fid_func, 'new_stats') else None
+        lstats = lpips.new_stats(names) if lpips is not None else None
         kept = [[], [], [], []] if fid_func is not None and fstats is None else None
         cnt = nbatch = 0
         shape = None                                           # (a rank whose share is empty never sees one; rank 0, which prints, has batch 0)
@@ -728,6 +732,8 @@ class DecolorTrainer(Trainer):
                 sets = [F.interpolate(z, size=64) for z in sets]
             sets = [z.repeat(1, 3 // z.shape[1], 1, 1) for z in sets]
             stats.add(sets[0], sets[1:])
+            if lstats is not None:
+                lstats.add(sets[0], sets[1:], lpips.model)
             if kept is not None:
                 for dst, z in zip(kept, sets):
                     dst.append((z + 1) * 0.5)
@@ -737,9 +743,13 @@ class DecolorTrainer(Trainer):
                 shape = sets[0].shape[1:]
         if world > 1:
             stats.all_reduce(device=self.device)
+            if lstats is not None:
+                lstats.all_reduce(device=self.device)
             for st in fstats or ():
                 st.all_reduce()
         out = stats.result()
+        if lstats is not None:
+            out.update(lstats.result())
         if kept is not None:
             orig, *cands = (torch.cat(z, dim=0) for z in kept)
             for z in [orig] + cands:
@@ -762,6 +772,8 @@ class DecolorTrainer(Trainer):
                     f"{prdc['precision']} / {prdc['recall']} / {prdc['density']} / {prdc['coverage']} / {prdc['f_score']}")
             say(f"The RMSE of {word} images with original image is {out[f'rmse_{name}']}")
             say(f"The SSIM of {word} images with original image is {out[f'ssim_{name}']}")
+            if lstats is not None:
+                say(f"The LPIPS of {word} images with original image is {out[f'lpips_{name}']}")
             if fid_func is not None and name != 'blur':
                 say(f"Hence the improvement in FID using {'sampling' if name == 'deblur' else 'direct sampling'} is "
                     f"{out['fid_blur'] - out[f'fid_{name}']}")

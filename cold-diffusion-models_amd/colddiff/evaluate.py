@@ -43,6 +43,13 @@ def _create_folder(path):
     os.makedirs(path, exist_ok=True)
 
 
+def check_lpips_sweep(lpips, fid_func):
+    """A sweep with `lpips=` runs on the per-batch device accumulators: its fid_func must be None or feed `FidStats`."""
+    if lpips is not None and fid_func is not None and not hasattr(fid_func, 'new_stats'):
+        raise ValueError("lpips= takes fid_func=None or a fid_func with new_stats (metrics.DeviceFid): the sweep then runs batch by batch "
+                         "on device accumulators and keeps no image set for a plain callable")
+
+
 def shard_ranks(shard, fid_func=None):
     """(rank, world) an evaluation sweep splits its batches over: (0, 1) unless `shard` is set AND the process is one of several of an
     initialised process group (`python -m torch.distributed.run`).  A sharded sweep merges per-rank accumulators, so its fid_func must be
@@ -168,7 +175,7 @@ class EvalMixin:
         return xt, direct_recons, all_images
 
     # -- DEBLUR:1567-1702 ---------------------------------------------------------------------------------------------
-    def fid_distance_decrease_from_manifold(self, fid_func=None, start=0, end=1000, batch=32, shard=False):
+    def fid_distance_decrease_from_manifold(self, fid_func=None, start=0, end=1000, batch=32, shard=False, lpips=None):
         """Degrade -> restore every dataset image in (start, end]; RMSE / SSIM (/ FID when fid_func is given) of the degraded, the
         sampled and the directly reconstructed images against the originals.  Returns the numbers the reference prints.
         A fid_func with `new_stats` (`metrics.DeviceFid`) is fed batch by batch -- four `FidStats` with the originals' features computed
@@ -177,10 +184,13 @@ class EvalMixin:
         one that has `prdc` (`metrics.DeviceFidKidPrdc`) adds `precision_<name>`, `recall_<name>`, `density_<name>`, `coverage_<name>`,
         `f_score_<name>` and one more line.
         `shard`: under `torch.distributed.run` with W > 1 ranks, rank r runs the batches k with k % W == r, the accumulators are
-        all-reduced at the end, every rank returns the same dict and rank 0 prints (fid_func: None or one with `new_stats`)."""
+        all-reduced at the end, every rank returns the same dict and rank 0 prints (fid_func: None or one with `new_stats`).
+        `lpips`: a `metrics.DeviceLpips` adds `lpips_<name>` and one printed line per name, from the same four [-1, 1] sets on the
+        per-batch device path (fid_func: None or one with `new_stats`)."""
+        check_lpips_sweep(lpips, fid_func)
         rank, world = shard_ranks(shard, fid_func)
-        if hasattr(fid_func, 'new_stats') or world > 1:
-            return self._fid_sweep_on_device(fid_func, start, end, batch, rank, world)
+        if hasattr(fid_func, 'new_stats') or world > 1 or lpips is not None:
+            return self._fid_sweep_on_device(fid_func, start, end, batch, rank, world, lpips)
         items = []
         for idx in range(len(self.ds)):
             if idx > start:
@@ -213,7 +223,7 @@ class EvalMixin:
             print(f"Hence the improvement in FID using direct sampling is {out['fid_blur'] - out['fid_direct_deblur']}")
         return out
 
-    def _fid_sweep_on_device(self, fid, start, end, batch, rank=0, world=1):
+    def _fid_sweep_on_device(self, fid, start, end, batch, rank=0, world=1, lpips=None):
         """The sweep on per-batch accumulators.  world > 1: this rank's share of the batches (every `world`-th, from `rank`; possibly
         none), then one all-reduce of the accumulators; `fid` may be None then (RMSE / SSIM only)."""
         items = []
@@ -226,6 +236,7 @@ class EvalMixin:
         names = ('blur', 'deblur', 'direct_deblur')
         pairs = metrics.PairStats(names)
         fstats = [fid.new_stats() for _ in range(4)] if fid is not None else []
+        lstats = lpips.new_stats(names) if lpips is not None else None
         rep3 = lambda z: z.repeat(1, 3 // z.shape[1], 1, 1)
         cnt = nbatch = 0
         while cnt < all_samples.shape[0]:
@@ -236,20 +247,28 @@ class EvalMixin:
             X_0s, X_ts = self.ema_core.all_sample(batch_size=og_img.shape[0], img=og_img, times=None)
             sets = [rep3(z.to(self.device)) for z in (og_img, X_ts[0], X_0s[-1], X_0s[0])]
             pairs.add(sets[0], sets[1:])
+            if lstats is not None:
+                lstats.add(sets[0], sets[1:], lpips.model)
             for st, z in zip(fstats, sets):
                 st.add_images((z + 1) * 0.5, fid.model, fid.batch_size)
         if world > 1:
             pairs.all_reduce(device=self.device)
+            if lstats is not None:
+                lstats.all_reduce(device=self.device)
             for st in fstats:
                 st.all_reduce()
         say = print if rank == 0 else (lambda *a, **kw: None)
         res, out = pairs.result(), {}
+        lres = lstats.result() if lstats is not None else {}
         for k, name in enumerate(names):
             out[f'rmse_{name}'], out[f'ssim_{name}'] = res[f'rmse_{name}'], res[f'ssim_{name}']
             if fid is not None:
                 out[f'fid_{name}'] = float(fid.distance(fstats[0], fstats[k + 1]))
             say(f"The RMSE of {name} images with original image is {out[f'rmse_{name}']}")
             say(f"The SSIM of {name} images with original image is {out[f'ssim_{name}']}")
+            if lstats is not None:
+                out[f'lpips_{name}'] = lres[f'lpips_{name}']
+                say(f"The LPIPS of {name} images with original image is {out[f'lpips_{name}']}")
             if fid is not None:
                 say(f"The FID of {name} images with original image is {out[f'fid_{name}']}")
             if hasattr(fid, 'kid'):

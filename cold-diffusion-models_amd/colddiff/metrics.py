@@ -13,6 +13,8 @@
 * knn_sq / ball_counts / prdc_device / DeviceFidKidPrdc: improved precision and recall (torch-fidelity's `prc`) and density and coverage
   of the same rows -- k-th-neighbour radii and ball memberships from fp64 Gram tiles consumed in the epilogue (cdf_knn_sq_f64,
   cdf_ball_counts_f64), no n x n matrix, one host read of four integer sums.
+* LpipsStats / DeviceLpips: LPIPS v0.1 (AlexNet) of up to four candidate sets against the originals -- the network is colddiff.lpips.LPIPS
+  on the conv GEMM kernels, the distance arithmetic cdf_lpips_layer; per set an fp64 device sum of the per-image distances.
 * FID = Frechet distance between the Gaussians fitted to InceptionV3 activations: the network is colddiff.inception.InceptionV3 (the
   reference's Fid/inception.py on the HIP kernels); its pretrained `pt_inception-2015-12-05` weights are a download upstream and are
   read from a local file here ($COLDDIFF_FID_WEIGHTS / torch hub cache).  Any other feature extractor
@@ -168,6 +170,69 @@ class PairStats:
             out[f'rmse_{name}'] = math.sqrt(float(sums[0, k]) / self.count)
             out[f'ssim_{name}'] = float(sums[1, k]) / self.positions
         return out
+
+
+class LpipsStats:
+    """Running LPIPS of named candidate sets against the originals over the batches of a sweep: `add(orig, cands, model)` per batch (the
+    originals' features computed once, sums of the per-image distances kept on the device in fp64), `result()` at the end (the one host
+    read) -> {'lpips_<name>': the mean distance over the images}.  Batches are in [-1, 1], as PairStats takes them."""
+
+    def __init__(self, names):
+        self.names = tuple(names)
+        assert 1 <= len(self.names) <= 4
+        self.sums = None                 # [K] fp64 on the device
+        self.count = 0                   # images per set
+
+    def add(self, orig, cands, model):
+        assert len(cands) == len(self.names)
+        cur = model.distances(orig, cands).sum(1)
+        self.sums = cur if self.sums is None else self.sums + cur
+        self.count += orig.shape[0]
+
+    def merge(self, other):
+        """Adds the sums and the count of `other` (the same names; an instance without a batch adds nothing) -> self."""
+        assert other.names == self.names, "LpipsStats.merge: the candidate sets differ"
+        if other.sums is not None:
+            cur = other.sums.to(self.sums.device) if self.sums is not None else other.sums.clone()
+            self.sums = cur if self.sums is None else self.sums + cur
+        self.count += other.count
+        return self
+
+    def all_reduce(self, group=None, device=None):
+        """As PairStats.all_reduce: the sums of every rank added in rank order in fp64 on every rank.  -> self"""
+        world = _group_size(group)
+        if world == 1:
+            return self
+        dev = self.sums.device if self.sums is not None else torch.device(device) if device is not None else _exchange_device()
+        mine = torch.zeros(len(self.names) + 1, device=dev, dtype=torch.float64)
+        if self.sums is not None:
+            mine[:-1] = self.sums
+        mine[-1] = self.count
+        parts = _gather_rows(mine, group)
+        total = parts[0].clone()
+        for r in range(1, world):
+            total = total + parts[r]
+        self.sums, self.count = total[:-1].clone(), int(total[-1].cpu())
+        return self
+
+    def result(self):
+        assert self.sums is not None, "LpipsStats.result(): no batch was added"
+        sums = self.sums.cpu()
+        return {f'lpips_{name}': float(sums[k]) / self.count for k, name in enumerate(self.names)}
+
+
+class DeviceLpips:
+    """Holds the LPIPS network for the Trainers' evaluation sweeps (`lpips=`), which feed its `new_stats(names)` per batch.  model: a
+    `colddiff.lpips.LPIPS`; None builds one from **kw (`weights=`, `lin=`: raises FileNotFoundError without the two weight files)."""
+
+    def __init__(self, model=None, device='cuda:0', **kw):
+        if model is None:
+            from .lpips import LPIPS
+            model = LPIPS(**kw).to(device)
+        self.model = model
+
+    def new_stats(self, names):
+        return LpipsStats(names)
 
 
 # -- FID (Fid/fid_score.py) ------------------------------------------------------------------------------------------

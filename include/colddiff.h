@@ -28,7 +28,7 @@ extern "C" {
 /* Bumped whenever an exported signature changes incompatibly (rounds 1-3 all answered 1 while arguments were added: `tiled`,
  * `onepass`, `slots`, `tune`).  cdf_abi_version() returns the value the LIBRARY was built with; a binding compares it with the
  * header it was generated from before the first call (colddiff/_lib.py does) -- a mismatched pair would read shifted arguments. */
-#define CDF_ABI_VERSION 16
+#define CDF_ABI_VERSION 17
 
 #define CDF_E_INVALID (-1)
 #define CDF_E_UNSUPPORTED (-2)
@@ -494,6 +494,26 @@ int cdf_knn_sq_f64(const double* x, int ldx, int n, int d, int k, const double* 
 int cdf_ball_splits(int na, int nb);
 int cdf_ball_counts_f64(const double* a, int lda, int na, const double* anorm, const double* b, int ldb, int nb, const double* bnorm, int d,
                         const double* rcol, const double* rrow, int* partial, int* cnt_col, int* cnt_row, void* stream);
+
+/* LPIPS v0.1 with the AlexNet backbone (Zhang et al. 2018; the `lpips` package's net = 'alex') on the device (colddiff/lpips.py,
+ * colddiff/metrics.py LpipsStats): what the metric adds to the conv GEMM kernels that run the network.
+ * cdf_lpips_prep_nhwc: x [B,3,H,W] NCHW fp32 in [-1, 1] -> y [B,H,W] pixels of pitch ldy, channels 0..2 = (x_c - shift_c) / scale_c with
+ * shift = (-.030, -.088, -.188), scale = (.458, .448, .450), channel 3 = 0 (the 4-channel zero-padded map the conv kernels take; channels
+ * past 3 of a wider pitch are not written).  from01 != 0: x is in [0, 1] and is mapped 2 x - 1 first (the package's normalize=True).
+ * ldy % 4 == 0, ldy >= 4, y 16-byte aligned.
+ * cdf_lpips_layer: one tap of the distance.  a: the originals' feature map, NHWC fp32 [B][HW][C] with pixel pitch ld; c0..c3: K = 1...4
+ * candidate maps of the same shape and pitch (those past K are ignored and may be NULL); w [C]: the tap's channel weights.
+ *   dist[k][b] += (1 / HW) sum_p sum_c w_c (a_pc / (|a_p| + 1e-10) - ck_pc / (|ck_p| + 1e-10))^2,   |v_p| = sqrt(sum_c v_pc^2),
+ * dist [K][B] fp64, ACCUMULATED: zero it once, five launches build one LPIPS distance.  Per-pixel arithmetic is fp32 in that order (norm,
+ * + eps, divide, subtract, square, weight; an all-zero pixel normalises to 0), sums over pixels are fp64.  Every map is read once; the
+ * pitch padding (channels C..ld) is never read.  partial: K * B * cdf_lpips_layer_blocks(HW, C) doubles of scratch, every one written by
+ * the call (cdf_lpips_layer_blocks: 0 for an HW or C the entry point refuses).  No atomics, every sum in a fixed order: two runs are
+ * bit-identical.  C % 4 == 0, 4 <= C <= 512, ld % 4 == 0, ld >= C, B in [1, 65535], HW >= 1, maps and w 16-byte aligned.  FEATURES MUST BE
+ * FINITE: not checked.  Evaluation-time calls, never a training or sampler step's. */
+int cdf_lpips_prep_nhwc(const float* x, float* y, int ldy, int B, int H, int W, int from01, void* stream);
+int cdf_lpips_layer_blocks(int HW, int C);
+int cdf_lpips_layer(const float* a, const float* c0, const float* c1, const float* c2, const float* c3, int K, int ld, const float* w,
+                    int B, int HW, int C, double* partial, double* dist, void* stream);
 
 /* parameter layout <-> GEMM layout: dst[t][r][c] = src[c*s_c + r*s_r + t*s_t] (c >= C zero-filled up to ldc);
  * g[c*s_c + r*s_r + t*s_t] (+)= sum_z ws[z][t][r][c] */
