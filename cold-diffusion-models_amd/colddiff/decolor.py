@@ -17,8 +17,10 @@ import torch
 from torch import nn
 
 from . import degrade as D
+from . import metrics
 from . import runtime as rt
 from .diffusion import TwoPhase, _full_step
+from .evaluate import rep3, sweep_ranks
 from .runtime import P
 from .trainer import Recipe, Trainer
 from .unet import Unet, exists
@@ -678,105 +680,69 @@ class DecolorTrainer(Trainer):
         the originals.  The items are the dataset's own (upstream does not pass them through `post_process_func`: with `to_lab` the
         network is fed RGB -- reproduced).  The sampler runs in its ends-only mode and the two metrics accumulate per batch
         (`metrics.PairStats`: one launch per batch, one host read at the end); the four sets are kept, on the device, only for a plain
-        fid_func.  A fid_func with `new_stats` (`metrics.DeviceFid`) is fed per batch instead: four `FidStats`, the originals' features
-        computed once, no set kept, three `distance` calls at the end; one that also has `kid` (`metrics.DeviceFidKid`) adds
-        `kid_<name>` / `kid_std_<name>` and a printed line after each `fid_<name>`; one that has `prdc`
-        (`metrics.DeviceFidKidPrdc`) adds `precision_<name>`, `recall_<name>`, `density_<name>`, `coverage_<name>`, `f_score_<name>` and
-        one more line.
-        `shard`: under `torch.distributed.run` with W > 1 ranks, rank r runs the batches k with k % W == r of rank 0's permutation (every
-        rank still draws its own, so its numpy stream advances as without the keyword), the accumulators are all-reduced at the end, every
-        rank returns the same dict and rank 0 prints (fid_func: None or one with `new_stats`).
-        `lpips`: a `metrics.DeviceLpips` adds `lpips_<name>` and one printed line per name, from the same four [-1, 1] sets per batch
-        (fid_func: None or one with `new_stats`).
+        fid_func.  A fid_func with `new_stats` / `kid` / `prdc`, `shard` and `lpips` are those of `EvalMixin`'s sweep of the same name
+        (`metrics.SweepStats`); sharded, the ranks walk rank 0's permutation (every rank still draws its own, so its numpy stream
+        advances as without the keyword).
         -> the numbers upstream prints."""
         import numpy as np
-        import torch.nn.functional as F
-        from . import metrics
-        from .evaluate import check_lpips_sweep, shard_ranks
-        check_lpips_sweep(lpips, fid_func)
-        rank, world = shard_ranks(shard, fid_func)
-        say = print if rank == 0 else (lambda *a, **kw: None)
+        rank, world, say = sweep_ranks(fid_func, shard, lpips)
         say(len(self.ds))
         perp = np.random.permutation(len(self.ds))
         if world > 1:
             walk = torch.from_numpy(perp).to(self.device)
             torch.distributed.broadcast(walk, src=0)
             perp = walk.cpu().numpy()
-        items = []
-        for idx in range(len(self.ds)):
-            img = self._dataset_item(int(perp[idx]))
-            if idx > start:
-                items.append(img)
+
+        def progress(idx, last):
             if idx % 1000 == 0:
                 say(idx)
-            if end != None and idx == end:                     # noqa: E711
+            if last:
                 say(idx)
-                break
-        all_samples = torch.stack(items)
+
+        all_samples = self._dataset_rows(start, end, every=True, fetch=lambda idx: self._dataset_item(int(perp[idx])), seen=progress)
         names = ('blur', 'deblur', 'direct_deblur')
-        stats = metrics.PairStats(names)
-        fstats = [fid_func.new_stats() for _ in range(4)] if hasattr(fid_func, 'new_stats') else None
-        lstats = lpips.new_stats(names) if lpips is not None else None
-        kept = [[], [], [], []] if fid_func is not None and fstats is None else None
-        cnt = nbatch = 0
+        stats = metrics.SweepStats(names, fid_func, lpips, keep=fid_func is not None and not hasattr(fid_func, 'new_stats'))
         shape = None                                           # (a rank whose share is empty never sees one; rank 0, which prints, has batch 0)
-        while cnt < all_samples.shape[0]:
-            og_img = all_samples[cnt: cnt + eval_batch_size].float()
-            cnt, nbatch = cnt + og_img.shape[0], nbatch + 1
-            if (nbatch - 1) % world != rank:
+        for k, og_img in enumerate(all_samples.split(eval_batch_size)):
+            if k % world != rank:
                 continue
+            og_img = og_img.float()
             say(og_img.shape)
             xt, direct, final = self.ema_core.all_sample(batch_size=og_img.shape[0], img=og_img, times=None, ends_only=True)
             sets = [og_img, xt, final, direct]
             if og_img.shape[2] > 256:
-                sets = [F.interpolate(z, size=64) for z in sets]
-            sets = [z.repeat(1, 3 // z.shape[1], 1, 1) for z in sets]
-            stats.add(sets[0], sets[1:])
-            if lstats is not None:
-                lstats.add(sets[0], sets[1:], lpips.model)
-            if kept is not None:
-                for dst, z in zip(kept, sets):
-                    dst.append((z + 1) * 0.5)
-            if fstats is not None:
-                for st, z in zip(fstats, sets):
-                    st.add_images((z + 1) * 0.5, fid_func.model, fid_func.batch_size)
-                shape = sets[0].shape[1:]
+                sets = [nn.functional.interpolate(z, size=64) for z in sets]
+            sets = [rep3(z) for z in sets]
+            stats.add(sets)
+            shape = sets[0].shape[1:]
         if world > 1:
-            stats.all_reduce(device=self.device)
-            if lstats is not None:
-                lstats.all_reduce(device=self.device)
-            for st in fstats or ():
-                st.all_reduce()
-        out = stats.result()
-        if lstats is not None:
-            out.update(lstats.result())
-        if kept is not None:
-            orig, *cands = (torch.cat(z, dim=0) for z in kept)
-            for z in [orig] + cands:
+            stats.all_reduce(self.device)
+        out = stats.pairs.result()
+        if lpips is not None:
+            out.update(stats.lstats.result())
+        if stats.sets is not None:
+            for z in stats.kept():
                 print(z.shape)
-        if fstats is not None and rank == 0:
-            for st in fstats:
+        if stats.fstats and rank == 0:
+            for st in stats.fstats:
                 print(torch.Size((st.n, *shape)))
         for k, (name, word) in enumerate(zip(names, ('blurry', 'deblurred', 'direct deblurred'))):
             if fid_func is not None:
-                out[f'fid_{name}'] = fid_func.distance(fstats[0], fstats[k + 1]) if fstats is not None else fid_func(samples=[orig, cands[k]])
-                say(f"The FID of {word} images with original image is {out[f'fid_{name}']}")
-            if hasattr(fid_func, 'kid'):
-                out[f'kid_{name}'], out[f'kid_std_{name}'] = fid_func.kid(fstats[0], fstats[k + 1])
-                say(f"The KID of {word} images with original image is {out[f'kid_{name}']} +- {out[f'kid_std_{name}']}")
-            if hasattr(fid_func, 'prdc'):
-                prdc = fid_func.prdc(fstats[0], fstats[k + 1])
-                for key in ('precision', 'recall', 'density', 'coverage', 'f_score'):
-                    out[f'{key}_{name}'] = prdc[key]
-                say(f"The precision / recall / density / coverage / F-score of {word} images with original image is "
-                    f"{prdc['precision']} / {prdc['recall']} / {prdc['density']} / {prdc['coverage']} / {prdc['f_score']}")
-            say(f"The RMSE of {word} images with original image is {out[f'rmse_{name}']}")
-            say(f"The SSIM of {word} images with original image is {out[f'ssim_{name}']}")
-            if lstats is not None:
-                say(f"The LPIPS of {word} images with original image is {out[f'lpips_{name}']}")
+                out[f'fid_{name}'] = stats.fid(k)
+                say(metrics.metric_line('FID', word, out[f'fid_{name}']))
+            if stats.has_kid:
+                out[f'kid_{name}'], out[f'kid_std_{name}'] = stats.kid(k)
+                say(metrics.metric_line('KID', word, out[f'kid_{name}'], out[f'kid_std_{name}']))
+            if stats.has_prdc:
+                prdc = stats.prdc(k)
+                metrics.put_prdc(out, name, prdc)
+                say(metrics.prdc_line(word, prdc))
+            say(metrics.metric_line('RMSE', word, out[f'rmse_{name}']))
+            say(metrics.metric_line('SSIM', word, out[f'ssim_{name}']))
+            if lpips is not None:
+                say(metrics.metric_line('LPIPS', word, out[f'lpips_{name}']))
             if fid_func is not None and name != 'blur':
-                say(f"Hence the improvement in FID using {'sampling' if name == 'deblur' else 'direct sampling'} is "
-                    f"{out['fid_blur'] - out[f'fid_{name}']}")
+                say(metrics.fid_gain_line(out, name))
         return out
 
     # figure code (cv2 text, matplotlib) and the two methods that are dead upstream (`metrics` is never imported there): closed, with the

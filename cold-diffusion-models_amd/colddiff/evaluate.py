@@ -43,11 +43,10 @@ def _create_folder(path):
     os.makedirs(path, exist_ok=True)
 
 
-def check_lpips_sweep(lpips, fid_func):
-    """A sweep with `lpips=` runs on the per-batch device accumulators: its fid_func must be None or feed `FidStats`."""
-    if lpips is not None and fid_func is not None and not hasattr(fid_func, 'new_stats'):
-        raise ValueError("lpips= takes fid_func=None or a fid_func with new_stats (metrics.DeviceFid): the sweep then runs batch by batch "
-                         "on device accumulators and keeps no image set for a plain callable")
+def require_fed(fid_func, asked, why):
+    """What `asked` for the per-batch accumulators ('lpips=', 'shard=True') needs: fid_func None or one that feeds `FidStats` (`new_stats`)."""
+    if fid_func is not None and not hasattr(fid_func, 'new_stats'):
+        raise ValueError(f"{asked} takes fid_func=None or a fid_func with new_stats (metrics.DeviceFid): {why}")
 
 
 def shard_ranks(shard, fid_func=None):
@@ -57,10 +56,21 @@ def shard_ranks(shard, fid_func=None):
     import torch.distributed as dist
     if not shard or not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() == 1:
         return 0, 1
-    if fid_func is not None and not hasattr(fid_func, 'new_stats'):
-        raise ValueError("shard=True takes fid_func=None or a fid_func with new_stats (metrics.DeviceFid): a plain callable needs the "
-                         "whole image sets, and every rank holds only its own batches")
+    require_fed(fid_func, "shard=True", "a plain callable needs the whole image sets, and every rank holds only its own batches")
     return dist.get_rank(), dist.get_world_size()
+
+
+def sweep_ranks(fid_func, shard, lpips):
+    """The checks both `fid_distance_decrease_from_manifold` sweeps open with -> (rank, world, say): `say` prints on rank 0 only."""
+    if lpips is not None:
+        require_fed(fid_func, "lpips=", "the sweep then runs batch by batch on device accumulators and keeps no image set for a plain callable")
+    rank, world = shard_ranks(shard, fid_func)
+    return rank, world, print if rank == 0 else (lambda *a, **kw: None)
+
+
+def rep3(z):
+    """A 1-channel batch repeated to the 3 channels the metrics take (a 3-channel batch as it is)."""
+    return z.repeat(1, 3 // z.shape[1], 1, 1)
 
 
 class EvalMixin:
@@ -83,8 +93,8 @@ class EvalMixin:
             yield img.to(self.device)
 
     def _dataset_item(self, idx):
-        from .trainer import DeviceImageCache
         """self.ds[idx] (DEBLUR:1578, 1717): the dataset's own transform chain -- a random crop where the dataset augments."""
+        from .trainer import DeviceImageCache
         if isinstance(self.ds, DeviceImageCache):
             if self.ds.recipe.crop == 'center' and not self.ds.recipe.flip:
                 return self.ds.item(idx)
@@ -93,6 +103,24 @@ class EvalMixin:
             dl.order, dl.pos = torch.tensor([idx], device=self.ds.data.device), 0
             return next(dl)[0]
         return self.ds[idx].to(self.device)
+
+    def _dataset_rows(self, start, end, every=False, fetch=None, seen=None):
+        """The dataset items idx with start < idx <= end, stacked (upstream's `if idx > start` / `if idx == end: break`).  `fetch(idx)`
+        gets one (default: `_dataset_item`); every=True calls it for every idx up to `end`, kept or not, as the upstream loops that do
+        so -- a dataset that augments through torch's global generator advances its stream per fetch.  `seen(idx, last)` after each idx."""
+        fetch = self._dataset_item if fetch is None else fetch
+        rows = []
+        for idx in range(len(self.ds)):
+            if every or idx > start:
+                img = fetch(idx)
+            if idx > start:
+                rows.append(img)
+            last = end is not None and idx == end
+            if seen is not None:
+                seen(idx, last)
+            if last:
+                break
+        return torch.stack(rows)
 
     def _save(self, img, name, nrow=6):
         from .trainer import save_image
@@ -187,102 +215,50 @@ class EvalMixin:
         all-reduced at the end, every rank returns the same dict and rank 0 prints (fid_func: None or one with `new_stats`).
         `lpips`: a `metrics.DeviceLpips` adds `lpips_<name>` and one printed line per name, from the same four [-1, 1] sets on the
         per-batch device path (fid_func: None or one with `new_stats`)."""
-        check_lpips_sweep(lpips, fid_func)
-        rank, world = shard_ranks(shard, fid_func)
-        if hasattr(fid_func, 'new_stats') or world > 1 or lpips is not None:
-            return self._fid_sweep_on_device(fid_func, start, end, batch, rank, world, lpips)
-        items = []
-        for idx in range(len(self.ds)):
-            if idx > start:
-                items.append(self._dataset_item(idx))
-            if end is not None and idx == end:
-                break
-        all_samples = torch.stack(items)
-        orig, blurred, deblurred, direct = [], [], [], []
-        rep3 = lambda z: z.repeat(1, 3 // z.shape[1], 1, 1)
-        cnt = 0
-        while cnt < all_samples.shape[0]:
-            og_img = all_samples[cnt: cnt + batch].float()
-            X_0s, X_ts = self.ema_core.all_sample(batch_size=og_img.shape[0], img=og_img, times=None)
-            for dst, z in ((orig, og_img), (blurred, X_ts[0]), (deblurred, X_0s[-1]), (direct, X_0s[0])):
-                dst.append((rep3(z.to(self.device)) + 1) * 0.5)
-            cnt += og_img.shape[0]
-        orig, blurred, deblurred, direct = (torch.cat(z, dim=0) for z in (orig, blurred, deblurred, direct))
-        out = {}
-        for name, z in (('blur', blurred), ('deblur', deblurred), ('direct_deblur', direct)):
-            out[f'rmse_{name}'] = float(metrics.rmse(orig, z))
-            out[f'ssim_{name}'] = float(metrics.ssim(orig, z, data_range=1, size_average=True))
-            if fid_func is not None:
-                out[f'fid_{name}'] = float(fid_func(samples=[orig, z]))
-            print(f"The RMSE of {name} images with original image is {out[f'rmse_{name}']}")
-            print(f"The SSIM of {name} images with original image is {out[f'ssim_{name}']}")
-            if fid_func is not None:
-                print(f"The FID of {name} images with original image is {out[f'fid_{name}']}")
-        if fid_func is not None:
-            print(f"Hence the improvement in FID using sampling is {out['fid_blur'] - out['fid_deblur']}")
-            print(f"Hence the improvement in FID using direct sampling is {out['fid_blur'] - out['fid_direct_deblur']}")
-        return out
-
-    def _fid_sweep_on_device(self, fid, start, end, batch, rank=0, world=1, lpips=None):
-        """The sweep on per-batch accumulators.  world > 1: this rank's share of the batches (every `world`-th, from `rank`; possibly
-        none), then one all-reduce of the accumulators; `fid` may be None then (RMSE / SSIM only)."""
-        items = []
-        for idx in range(len(self.ds)):
-            if idx > start:
-                items.append(self._dataset_item(idx))
-            if end is not None and idx == end:
-                break
-        all_samples = torch.stack(items)
+        rank, world, say = sweep_ranks(fid_func, shard, lpips)
+        # fed: per-batch accumulators, one all-reduce.  Otherwise the whole-set path: rmse / ssim / a plain callable on the concatenated sets
+        fed = hasattr(fid_func, 'new_stats') or world > 1 or lpips is not None
         names = ('blur', 'deblur', 'direct_deblur')
-        pairs = metrics.PairStats(names)
-        fstats = [fid.new_stats() for _ in range(4)] if fid is not None else []
-        lstats = lpips.new_stats(names) if lpips is not None else None
-        rep3 = lambda z: z.repeat(1, 3 // z.shape[1], 1, 1)
-        cnt = nbatch = 0
-        while cnt < all_samples.shape[0]:
-            og_img = all_samples[cnt: cnt + batch].float()
-            cnt, nbatch = cnt + og_img.shape[0], nbatch + 1
-            if (nbatch - 1) % world != rank:
+        stats = metrics.SweepStats(names, fid_func, lpips, keep=not fed, pairs=fed)
+        for k, og_img in enumerate(self._dataset_rows(start, end).split(batch)):
+            if k % world != rank:
                 continue
+            og_img = og_img.float()
             X_0s, X_ts = self.ema_core.all_sample(batch_size=og_img.shape[0], img=og_img, times=None)
-            sets = [rep3(z.to(self.device)) for z in (og_img, X_ts[0], X_0s[-1], X_0s[0])]
-            pairs.add(sets[0], sets[1:])
-            if lstats is not None:
-                lstats.add(sets[0], sets[1:], lpips.model)
-            for st, z in zip(fstats, sets):
-                st.add_images((z + 1) * 0.5, fid.model, fid.batch_size)
+            stats.add([rep3(z.to(self.device)) for z in (og_img, X_ts[0], X_0s[-1], X_0s[0])])
         if world > 1:
-            pairs.all_reduce(device=self.device)
-            if lstats is not None:
-                lstats.all_reduce(device=self.device)
-            for st in fstats:
-                st.all_reduce()
-        say = print if rank == 0 else (lambda *a, **kw: None)
-        res, out = pairs.result(), {}
-        lres = lstats.result() if lstats is not None else {}
+            stats.all_reduce(self.device)
+        if fed:
+            res = stats.pairs.result()
+            lres = stats.lstats.result() if lpips is not None else {}
+        else:
+            orig, *cands = stats.kept()
+        out = {}
         for k, name in enumerate(names):
-            out[f'rmse_{name}'], out[f'ssim_{name}'] = res[f'rmse_{name}'], res[f'ssim_{name}']
-            if fid is not None:
-                out[f'fid_{name}'] = float(fid.distance(fstats[0], fstats[k + 1]))
-            say(f"The RMSE of {name} images with original image is {out[f'rmse_{name}']}")
-            say(f"The SSIM of {name} images with original image is {out[f'ssim_{name}']}")
-            if lstats is not None:
+            if fed:
+                out[f'rmse_{name}'], out[f'ssim_{name}'] = res[f'rmse_{name}'], res[f'ssim_{name}']
+            else:
+                out[f'rmse_{name}'] = float(metrics.rmse(orig, cands[k]))
+                out[f'ssim_{name}'] = float(metrics.ssim(orig, cands[k], data_range=1, size_average=True))
+            if fid_func is not None:
+                out[f'fid_{name}'] = float(stats.fid(k))
+            say(metrics.metric_line('RMSE', name, out[f'rmse_{name}']))
+            say(metrics.metric_line('SSIM', name, out[f'ssim_{name}']))
+            if lpips is not None:
                 out[f'lpips_{name}'] = lres[f'lpips_{name}']
-                say(f"The LPIPS of {name} images with original image is {out[f'lpips_{name}']}")
-            if fid is not None:
-                say(f"The FID of {name} images with original image is {out[f'fid_{name}']}")
-            if hasattr(fid, 'kid'):
-                out[f'kid_{name}'], out[f'kid_std_{name}'] = fid.kid(fstats[0], fstats[k + 1])
-                say(f"The KID of {name} images with original image is {out[f'kid_{name}']} +- {out[f'kid_std_{name}']}")
-            if hasattr(fid, 'prdc'):
-                prdc = fid.prdc(fstats[0], fstats[k + 1])
-                for key in ('precision', 'recall', 'density', 'coverage', 'f_score'):
-                    out[f'{key}_{name}'] = prdc[key]
-                say(f"The precision / recall / density / coverage / F-score of {name} images with original image is "
-                    f"{prdc['precision']} / {prdc['recall']} / {prdc['density']} / {prdc['coverage']} / {prdc['f_score']}")
-        if fid is not None:
-            say(f"Hence the improvement in FID using sampling is {out['fid_blur'] - out['fid_deblur']}")
-            say(f"Hence the improvement in FID using direct sampling is {out['fid_blur'] - out['fid_direct_deblur']}")
+                say(metrics.metric_line('LPIPS', name, out[f'lpips_{name}']))
+            if fid_func is not None:
+                say(metrics.metric_line('FID', name, out[f'fid_{name}']))
+            if stats.has_kid:
+                out[f'kid_{name}'], out[f'kid_std_{name}'] = stats.kid(k)
+                say(metrics.metric_line('KID', name, out[f'kid_{name}'], out[f'kid_std_{name}']))
+            if stats.has_prdc:
+                prdc = stats.prdc(k)
+                metrics.put_prdc(out, name, prdc)
+                say(metrics.prdc_line(name, prdc))
+        if fid_func is not None:
+            say(metrics.fid_gain_line(out, 'deblur'))
+            say(metrics.fid_gain_line(out, 'direct_deblur'))
         return out
 
     # -- DEBLUR:1712-1722 ---------------------------------------------------------------------------------------------
@@ -340,16 +316,14 @@ class GenEvalMixin:
         """rows idx with start < idx <= end of the dataset (upstream's `if idx > start` / `if idx == end: break`), resampled to siz x siz
         (bilinear) and flattened when siz is given"""
         import torch.nn.functional as F
-        rows = []
-        for idx in range(len(self.ds)):
+
+        def fetch(idx):
             img = self._dataset_item(idx).unsqueeze(0)
             if siz is not None:
                 img = F.interpolate(img, size=siz, mode='bilinear').flatten(1)
-            if idx > start:
-                rows.append(img[0])
-            if end is not None and idx == end:
-                break
-        return torch.stack(rows)
+            return img[0]
+
+        return self._dataset_rows(start, end, every=True, fetch=fetch)
 
     def _sk_gmm(self, feats, clusters, device_gmm=False):
         """scikit-learn's mixture on the host as upstream; device_gmm: `colddiff.gmm.GaussianMixture` with scikit-learn's defaults (tol 1e-3,

@@ -15,6 +15,9 @@
   cdf_ball_counts_f64), no n x n matrix, one host read of four integer sums.
 * LpipsStats / DeviceLpips: LPIPS v0.1 (AlexNet) of up to four candidate sets against the originals -- the network is colddiff.lpips.LPIPS
   on the conv GEMM kernels, the distance arithmetic cdf_lpips_layer; per set an fp64 device sum of the per-image distances.
+* _SumStats: the `merge` and the `all_reduce` PairStats and LpipsStats share.  SweepStats: the accumulators of one Trainer evaluation
+  sweep (a PairStats, the four `new_stats()` of the fid_func, an LpipsStats, the kept sets of a plain callable) behind `add(sets)`, one
+  `all_reduce` and per-set `fid` / `kid` / `prdc`; metric_line / prdc_line / fid_gain_line: the sentences the sweeps print.
 * FID = Frechet distance between the Gaussians fitted to InceptionV3 activations: the network is colddiff.inception.InceptionV3 (the
   reference's Fid/inception.py on the HIP kernels); its pretrained `pt_inception-2015-12-05` weights are a download upstream and are
   read from a local file here ($COLDDIFF_FID_WEIGHTS / torch hub cache).  Any other feature extractor
@@ -109,37 +112,31 @@ def _gather_rows(mine, group=None):
     return rows
 
 
-class PairStats:
-    """Running RMSE / SSIM of named candidate sets against the originals over the batches of a sweep: `add(orig, cands)` per batch (one
-    launch, sums kept on the device in fp64), `result()` at the end (the one host read) ->
-    {'rmse_<name>': sqrt(SSE / count), 'ssim_<name>': S / (planes (H - 10) (W - 10))}: the whole-set `rmse` and
-    `ssim(data_range=1, size_average=True)` of the concatenated sets up to summation order."""
+class _SumStats:
+    """What PairStats and LpipsStats share: `names`, `sums` -- an fp64 device tensor of shape `(*rows, K)`, None until the first batch --
+    and the Python-int attributes named in `counts`; the one `merge` and the one `all_reduce` of both."""
+    what = rows = counts = None          # set by the subclass: its name in messages, the leading shape of `sums`, the count attributes
 
-    def __init__(self, names, shift=True):
+    def __init__(self, names):
         self.names = tuple(names)
         assert 1 <= len(self.names) <= 4
-        self.shift = shift
-        self.sums = None                 # [2, K] fp64 on the device: SSE, SSIM sums
-        self.count = 0                   # values per set
-        self.positions = 0               # valid SSIM positions per set
+        self.sums = None
+        for c in self.counts:
+            setattr(self, c, 0)
 
-    def add(self, orig, cands):
-        assert len(cands) == len(self.names)
-        sse, ss = eval_pairs(orig, cands, shift=self.shift)
-        cur = torch.stack((sse, ss))
+    def _add(self, cur, *counts):
         self.sums = cur if self.sums is None else self.sums + cur
-        B, C, H, W = orig.shape
-        self.count += B * C * H * W
-        self.positions += B * C * (H - 10) * (W - 10)
+        for c, n in zip(self.counts, counts):
+            setattr(self, c, getattr(self, c) + n)
 
     def merge(self, other):
         """Adds the sums and counts of `other` (the same names; an instance without a batch adds nothing) -> self."""
-        assert other.names == self.names, "PairStats.merge: the candidate sets differ"
+        assert other.names == self.names, f"{self.what}.merge: the candidate sets differ"
         if other.sums is not None:
             cur = other.sums.to(self.sums.device) if self.sums is not None else other.sums.clone()
             self.sums = cur if self.sums is None else self.sums + cur
-        self.count += other.count
-        self.positions += other.positions
+        for c in self.counts:
+            setattr(self, c, getattr(self, c) + getattr(other, c))
         return self
 
     def all_reduce(self, group=None, device=None):
@@ -150,17 +147,38 @@ class PairStats:
         if world == 1:
             return self
         dev = self.sums.device if self.sums is not None else torch.device(device) if device is not None else _exchange_device()
-        mine = torch.zeros(2 * len(self.names) + 2, device=dev, dtype=torch.float64)
+        shape, n = (*self.rows, len(self.names)), len(self.counts)
+        mine = torch.zeros(math.prod(shape) + n, device=dev, dtype=torch.float64)      # sums.reshape(-1), then the counts
         if self.sums is not None:
-            mine[:-2] = self.sums.reshape(-1)
-        mine[-2], mine[-1] = self.count, self.positions              # (integers far below 2^53)
+            mine[:-n] = self.sums.reshape(-1)
+        mine[-n:] = torch.tensor([getattr(self, c) for c in self.counts], dtype=torch.float64)      # (integers far below 2^53)
         parts = _gather_rows(mine, group)
         total = parts[0].clone()
         for r in range(1, world):
             total = total + parts[r]
-        tail = total[-2:].cpu()
-        self.sums, self.count, self.positions = total[:-2].reshape(2, len(self.names)).clone(), int(tail[0]), int(tail[1])
+        self.sums = total[:-n].reshape(shape).clone()
+        for c, v in zip(self.counts, total[-n:].cpu()):
+            setattr(self, c, int(v))
         return self
+
+
+class PairStats(_SumStats):
+    """Running RMSE / SSIM of named candidate sets against the originals over the batches of a sweep: `add(orig, cands)` per batch (one
+    launch, sums kept on the device in fp64), `result()` at the end (the one host read) ->
+    {'rmse_<name>': sqrt(SSE / count), 'ssim_<name>': S / (planes (H - 10) (W - 10))}: the whole-set `rmse` and
+    `ssim(data_range=1, size_average=True)` of the concatenated sets up to summation order.
+    `sums` [2, K]: SSE, SSIM sums; `count`: values per set; `positions`: valid SSIM positions per set."""
+    what, rows, counts = 'PairStats', (2,), ('count', 'positions')
+
+    def __init__(self, names, shift=True):
+        super().__init__(names)
+        self.shift = shift
+
+    def add(self, orig, cands):
+        assert len(cands) == len(self.names)
+        sse, ss = eval_pairs(orig, cands, shift=self.shift)
+        B, C, H, W = orig.shape
+        self._add(torch.stack((sse, ss)), B * C * H * W, B * C * (H - 10) * (W - 10))
 
     def result(self):
         assert self.sums is not None, "PairStats.result(): no batch was added"
@@ -172,48 +190,16 @@ class PairStats:
         return out
 
 
-class LpipsStats:
+class LpipsStats(_SumStats):
     """Running LPIPS of named candidate sets against the originals over the batches of a sweep: `add(orig, cands, model)` per batch (the
     originals' features computed once, sums of the per-image distances kept on the device in fp64), `result()` at the end (the one host
-    read) -> {'lpips_<name>': the mean distance over the images}.  Batches are in [-1, 1], as PairStats takes them."""
-
-    def __init__(self, names):
-        self.names = tuple(names)
-        assert 1 <= len(self.names) <= 4
-        self.sums = None                 # [K] fp64 on the device
-        self.count = 0                   # images per set
+    read) -> {'lpips_<name>': the mean distance over the images}.  Batches are in [-1, 1], as PairStats takes them.
+    `sums` [K]; `count`: images per set."""
+    what, rows, counts = 'LpipsStats', (), ('count',)
 
     def add(self, orig, cands, model):
         assert len(cands) == len(self.names)
-        cur = model.distances(orig, cands).sum(1)
-        self.sums = cur if self.sums is None else self.sums + cur
-        self.count += orig.shape[0]
-
-    def merge(self, other):
-        """Adds the sums and the count of `other` (the same names; an instance without a batch adds nothing) -> self."""
-        assert other.names == self.names, "LpipsStats.merge: the candidate sets differ"
-        if other.sums is not None:
-            cur = other.sums.to(self.sums.device) if self.sums is not None else other.sums.clone()
-            self.sums = cur if self.sums is None else self.sums + cur
-        self.count += other.count
-        return self
-
-    def all_reduce(self, group=None, device=None):
-        """As PairStats.all_reduce: the sums of every rank added in rank order in fp64 on every rank.  -> self"""
-        world = _group_size(group)
-        if world == 1:
-            return self
-        dev = self.sums.device if self.sums is not None else torch.device(device) if device is not None else _exchange_device()
-        mine = torch.zeros(len(self.names) + 1, device=dev, dtype=torch.float64)
-        if self.sums is not None:
-            mine[:-1] = self.sums
-        mine[-1] = self.count
-        parts = _gather_rows(mine, group)
-        total = parts[0].clone()
-        for r in range(1, world):
-            total = total + parts[r]
-        self.sums, self.count = total[:-1].clone(), int(total[-1].cpu())
-        return self
+        self._add(model.distances(orig, cands).sum(1), orig.shape[0])
 
     def result(self):
         assert self.sums is not None, "LpipsStats.result(): no batch was added"
@@ -775,3 +761,75 @@ class DeviceFidKidPrdc(DeviceFidKid):
 
     def prdc(self, s1, s2):
         return prdc_device(s1.kid_stats, s2.kid_stats, self.prdc_k)
+
+
+# -- the accumulators and the printed lines of an evaluation sweep -----------------------------------------------------------------------
+class SweepStats:
+    """The accumulators of one `fid_distance_decrease_from_manifold` sweep over the originals and the candidate sets `names`: `pairs` (a
+    PairStats; None with pairs=False), `fstats` (one `fid.new_stats()` per set, the originals' first, when `fid` has `new_stats`), `lstats`
+    (`lpips.new_stats(names)` when `lpips` is given) and, with keep=True, the [0, 1] sets a plain callable `fid` and the whole-set metrics
+    need.  `fid(k)`, `kid(k)`, `prdc(k)` of candidate set k compute when asked: launches, host reads and lines fall where the sweep asks."""
+
+    def __init__(self, names, fid=None, lpips=None, keep=False, pairs=True):
+        self.names, self.fid_func, self.lpips = tuple(names), fid, lpips
+        self.pairs = PairStats(names) if pairs else None
+        self.fstats = [fid.new_stats() for _ in range(1 + len(self.names))] if hasattr(fid, 'new_stats') else []
+        self.lstats = lpips.new_stats(names) if lpips is not None else None
+        self.sets = [[] for _ in range(1 + len(self.names))] if keep else None
+        self.has_kid, self.has_prdc = hasattr(fid, 'kid'), hasattr(fid, 'prdc')
+
+    def add(self, sets):
+        """sets = [orig, *cands]: 3-channel batches in [-1, 1]."""
+        if self.pairs is not None:
+            self.pairs.add(sets[0], sets[1:])
+        if self.lstats is not None:
+            self.lstats.add(sets[0], sets[1:], self.lpips.model)
+        if self.sets is not None:
+            for dst, z in zip(self.sets, sets):
+                dst.append((z + 1) * 0.5)
+        for st, z in zip(self.fstats, sets):
+            st.add_images((z + 1) * 0.5, self.fid_func.model, self.fid_func.batch_size)
+
+    def all_reduce(self, device):
+        for st in (self.pairs, self.lstats):
+            if st is not None:
+                st.all_reduce(device=device)
+        for st in self.fstats:
+            st.all_reduce()
+
+    def kept(self):
+        """[orig, *cands] in [0, 1], each concatenated over the batches (keep=True): the one place a sweep concatenates image sets."""
+        if isinstance(self.sets[0], list):
+            self.sets = [torch.cat(z, dim=0) for z in self.sets]
+        return self.sets
+
+    def fid(self, k):
+        if self.fstats:
+            return self.fid_func.distance(self.fstats[0], self.fstats[k + 1])
+        return self.fid_func(samples=[self.kept()[0], self.kept()[k + 1]])
+
+    def kid(self, k):
+        return self.fid_func.kid(self.fstats[0], self.fstats[k + 1])
+
+    def prdc(self, k):
+        return self.fid_func.prdc(self.fstats[0], self.fstats[k + 1])
+
+
+PRDC_KEYS = ('precision', 'recall', 'density', 'coverage', 'f_score')
+
+
+def metric_line(metric, word, value, std=None):
+    """The sentence both sweeps print per metric and set; with `std` the KID form "value +- std"."""
+    return f"The {metric} of {word} images with original image is {value}" + ("" if std is None else f" +- {std}")
+
+
+def prdc_line(word, prdc):
+    return metric_line('precision / recall / density / coverage / F-score', word, ' / '.join(str(prdc[key]) for key in PRDC_KEYS))
+
+
+def put_prdc(out, name, prdc):
+    out.update({f'{key}_{name}': prdc[key] for key in PRDC_KEYS})
+
+
+def fid_gain_line(out, name):
+    return f"Hence the improvement in FID using {'sampling' if name == 'deblur' else 'direct sampling'} is {out['fid_blur'] - out[f'fid_{name}']}"
