@@ -42,9 +42,12 @@ import contextlib as _contextlib
 
 @_contextlib.contextmanager
 def precision_scope(p):
-    """Run a region in another arithmetic mode.  The packed-weight cache keeps ONE layout per (parameter, kind) and remembers the mode it
-    was packed in: the first use of a weight in the other mode packs it again over that slot (every kind, not only the bf16 planes whose
-    contents depend on the mode), and so does the first use after the region ends."""
+    """Run a region in another arithmetic mode.  The packed-weight cache keeps ONE layout per (parameter, kind) -- the mode is not part of
+    the slot -- and remembers the mode it was packed in: the first use of a weight in the other mode packs it again over that slot, and
+    so does the first use after the region ends.  That holds for every kind: the `_sp` kinds change their contents with the mode (the
+    lo plane exists in "bf16x3" only), the kinds without `_sp` (conv_fwd, kv_fwd, dw, lin_fwd, cin4 ...) hold the same values in every
+    mode, share their slot across the modes all the same and are re-packed, into the same buffer, by their own launch on each toggle
+    (pinned by tests/test_weight_caches.py::test_layout_precision_toggle_on_a_shared_slot)."""
     global precision
     assert p in ("f32", "bf16x3", "bf16"), p
     saved, precision = precision, p

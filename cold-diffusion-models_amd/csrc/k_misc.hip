@@ -347,9 +347,33 @@ extern "C" int cdf_scale(float* x, long long n, float s, void* stream) {
     CDF_LAUNCH(scale_kernel, dim3(cdf_ew_grid8k(n)), dim3(256), 0, CDF_S, x, n, s);
     return cdf_check_launch("scale");
 }
+// bytes [0, bytes) of p zeroed with plain stores: 16-byte groups from the first aligned address, the ragged ends byte by byte
+__global__ void zero_kernel(unsigned char* p, long long bytes) {
+    long long head = (long long)((16 - ((uintptr_t)p & 15)) & 15);
+    if (head > bytes) head = bytes;
+    const long long nvec = (bytes - head) / 16;
+    uint4* v = (uint4*)(p + head);
+    CDF_EW_LOOP(i, nvec) v[i] = make_uint4(0u, 0u, 0u, 0u);
+    if (blockIdx.x == 0) {
+        for (long long i = threadIdx.x; i < head; i += blockDim.x) p[i] = 0;
+        for (long long i = head + nvec * 16 + threadIdx.x; i < bytes; i += blockDim.x) p[i] = 0;
+    }
+}
 extern "C" int cdf_zero(void* p, long long bytes, void* stream) {
     CDF_REQUIRE(p && bytes >= 0, "cdf_zero: bad args");
     if (bytes == 0) return CDF_OK;
+#ifndef CDF_EMU
+    // Under stream capture the zeroing is a kernel node, not a memset node.  With the memset node, a graph-mode Trainer whose weights
+    // were read back to the host (pageable copies) between replays ended with denormal-size values (one pair, in lanes 1 and 2 of every
+    // 16-byte group no gradient is written to) in the gradient arena, and Adam carried them into exp_avg and the arena's alignment
+    // gaps; with the kernel node the arenas are bit for bit the eager Trainer's (tests/test_weight_caches.py, graph mode).  Why the
+    // replayed memset does that was not established; outside capture hipMemsetAsync stays.
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(CDF_S, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone) {
+        CDF_LAUNCH(zero_kernel, dim3(cdf_ew_grid8k((bytes + 15) / 16)), dim3(256), 0, CDF_S, (unsigned char*)p, bytes);
+        return cdf_check_launch("zero");
+    }
+#endif
     hipError_t e = hipMemsetAsync(p, 0, (size_t)bytes, CDF_S);
     if (e != hipSuccess) {
         cdf_set_error("cdf_zero: hipMemsetAsync failed: %s", hipGetErrorString(e));
