@@ -17,8 +17,9 @@ import torch
 from torch import nn
 
 from . import degrade as D
-from . import metrics
+from . import metrics, parallel
 from . import runtime as rt
+from .data import RANDOM_AUG, CacheUnfit, DeviceImageCache, DeviceLoader, cycle, make_grid, save_image, write_grid
 from .diffusion import TwoPhase, _full_step
 from .evaluate import rep3, sweep_ranks
 from .runtime import P
@@ -497,7 +498,7 @@ class DecolorTrainer(Trainer):
     """diffusion.py:563-760 on the shared Trainer (fused gradient accumulation, flat Adam / EMA, device image cache).  The default dataset
     chain is `CenterCrop(image_size)` on the file's own size; `to_lab=True` converts every batch with `cdf_lab_convert`; `random_aug`
     (RandomResizedCrop -> mirror -> RandomApply([ColorJitter])) runs on the device image cache in one launch per batch
-    (`cdf_augment_jitter_batch`, `trainer.RANDOM_AUG`) when `device_data` is on; with `device_data=False`, a folder the cache cannot hold,
+    (`cdf_augment_jitter_batch`, `data.RANDOM_AUG`) when `device_data` is on; with `device_data=False`, a folder the cache cannot hold,
     or `torchvision_dataset` (torchvision's dataset classes) it is the host `DataLoader`, which needs torchvision and raises an
     ImportError naming the option where that is missing."""
     image_size_from_model = False
@@ -535,8 +536,6 @@ class DecolorTrainer(Trainer):
             return super()._make_loader(folder, dataset, shuffle, num_workers, seed)
         if self.random_aug and not self.torchvision_dataset and self.device_data and folder is not None and dataset != 'synthetic':
             # the unresized RGB folder in HBM; RandomResizedCrop / mirror / ColorJitter / ToTensor per batch in one launch
-            from . import parallel
-            from .trainer import RANDOM_AUG, CacheUnfit, DeviceImageCache, DeviceLoader
             self.recipe = RANDOM_AUG
             try:
                 cache = DeviceImageCache(folder, self.data_image_size, self.device, recipe=RANDOM_AUG)
@@ -553,7 +552,6 @@ class DecolorTrainer(Trainer):
                               f"installed; the default CenterCrop chain runs without it") from e
         from torch.utils import data
         from . import decolor_data
-        from .trainer import cycle
         size = (self.data_image_size, self.data_image_size)
         if self.torchvision_dataset:
             ds = decolor_data.get_dataset(dataset, folder, size, random_aug=self.random_aug)
@@ -576,7 +574,6 @@ class DecolorTrainer(Trainer):
     # package's upstream: names, arguments, file names and print wording.  Titles (add_title: cv2 text) are left out.
     def _write_image(self, tensor, path, nrow=8):
         """The one place an evaluation image reaches a file: a ready [C,H,W] grid as it is, a [B,C,H,W] batch through `save_image`."""
-        from .trainer import save_image, write_grid
         if tensor.dim() == 3:
             write_grid(tensor.detach().float().cpu(), path)
         else:
@@ -586,7 +583,6 @@ class DecolorTrainer(Trainer):
         return (img + 1.0) / 2
 
     def save_og_test(self, og_dict, extra_path):
-        from .trainer import make_grid
         for k, img in og_dict.items():
             img_grid = make_grid((img + 1) * 0.5, nrow=6)
             self._write_image(img_grid, str(self.results_folder / f'{k}-{extra_path}.png'))
@@ -596,7 +592,6 @@ class DecolorTrainer(Trainer):
         """Per step the x0 and x_t grids, nested as upstream nests them -- (frame grid, og grid [, init_recon grid]) -- as PNGs, and the
         two GIFs of those files (through PIL; upstream: imageio)."""
         from PIL import Image
-        from .trainer import make_grid
         if init_recon is not None:
             init_recon = (init_recon + 1) * 0.5
         self.gif_len = len(X_0s)
@@ -772,7 +767,6 @@ class DecolorTrainer(Trainer):
                  "paper_showing_diffusion_images_cover_page")
 
     def save(self, save_with_time_stamp=False):
-        from . import parallel
         if parallel.rank() != 0:
             return
         ckpt = {'step': self.step, 'model': self.model.state_dict(), 'ema': self.ema_model.state_dict()}
@@ -780,8 +774,6 @@ class DecolorTrainer(Trainer):
         torch.save(ckpt, str(self.results_folder / name))
 
     def train(self):
-        from . import parallel
-        from .trainer import save_image
         while self.step < self.train_num_steps:
             loss = self.train_step()
             if not self.quiet and parallel.rank() == 0 and self.step % 100 == 0:

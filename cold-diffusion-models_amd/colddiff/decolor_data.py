@@ -2,7 +2,7 @@
 `Trainer(torchvision_dataset=True)` reads CIFAR-10 / CelebA / Flowers102 through torchvision's dataset classes, `Trainer(random_aug=True)`
 adds RandomResizedCrop + ColorJitter.  Both are host-side PIL pipelines; torchvision is imported when one of them is asked for, and a
 missing torchvision is an ImportError that names the option.  The default chain (CenterCrop, ToTensor, t * 2 - 1) does not come through
-here: it is a `trainer.Recipe` on the device image cache."""
+here: it is a `data.Recipe` on the device image cache."""
 from pathlib import Path
 
 from torch.utils import data

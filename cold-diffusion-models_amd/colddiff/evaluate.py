@@ -12,8 +12,9 @@ import os
 
 import torch
 
-from . import metrics
+from . import metrics, parallel
 from . import runtime as rt
+from .data import DeviceImageCache, DeviceLoader, save_image
 
 
 class GMM:
@@ -80,7 +81,6 @@ class EvalMixin:
     def _dataset_batches(self, batch_size):
         """The dataset in order in batches of `batch_size` (drop_last=True), as `DataLoader(self.ds, shuffle=False, drop_last=True)`
         yields them (DEBLUR:1396-1397); from the device cache when the folder lives in HBM."""
-        from .trainer import DeviceImageCache, DeviceLoader
         assert self.ds is not None, "this evaluation method needs an image folder (the Trainer was built on synthetic data)"
         batch_size = min(batch_size, len(self.ds))            # (upstream hard-codes 100 with drop_last: smaller folders would yield nothing)
         if isinstance(self.ds, DeviceImageCache):
@@ -94,11 +94,9 @@ class EvalMixin:
 
     def _dataset_item(self, idx):
         """self.ds[idx] (DEBLUR:1578, 1717): the dataset's own transform chain -- a random crop where the dataset augments."""
-        from .trainer import DeviceImageCache
         if isinstance(self.ds, DeviceImageCache):
             if self.ds.recipe.crop == 'center' and not self.ds.recipe.flip:
                 return self.ds.item(idx)
-            from .trainer import DeviceLoader
             dl = DeviceLoader(self.ds, 1, shuffle=False, seed=123457 + idx)
             dl.order, dl.pos = torch.tensor([idx], device=self.ds.data.device), 0
             return next(dl)[0]
@@ -123,7 +121,6 @@ class EvalMixin:
         return torch.stack(rows)
 
     def _save(self, img, name, nrow=6):
-        from .trainer import save_image
         save_image((img + 1) * 0.5, name, nrow=nrow)
 
     def _fit_gmm(self, torch_gmm, feats, clusters, batch_size, **extra):
@@ -298,7 +295,6 @@ class GenEvalMixin:
                     self._save(all_images[i:i + 1], f'{out_folder}/sample-x0-{cnt + i}.png', nrow=1)
             cnt += all_images.shape[0] if world == 1 else bs          # (sharded: the count cannot depend on a round another rank ran)
         if world > 1:
-            from . import parallel
             parallel.milestone_barrier()
         return cnt
 

@@ -46,8 +46,8 @@ def new_feat(ref, B, H, W, C, zero=False):
 # happened; writes through torch move the version counter and need no bump.  The sites that write raw and bump:
 #   flat.FlatArena.__init__ (re-homes the parameters), flat.FusedAdam.step (cdf_adam_step), flat.ema_update (cdf_ema_update),
 #   trainer.Trainer.__init__ (the broadcast of rank 0's arena), Trainer.reset_parameters (arena copy), Trainer.load,
-#   Trainer._graph_train_step (cdf_adam_step_dev leaves the bump to it: once after a capture pass, which marked layouts current
-#   without writing them, and once per real step, replayed or not).  bench.py bumps around its mode changes, which write nothing
+#   Trainer._graph_capture_pass and Trainer.train_step (cdf_adam_step_dev leaves the bump to them: once after a capture pass, which
+#   marked layouts current without writing them, and once per real graph-mode step, replayed or not).  bench.py bumps around its mode changes, which write nothing
 #   (the mode is compared per layout): harmless, one refresh each.
 # tests/test_weight_caches.py walks the state machine below with random event sequences against a cold start.
 _pack_cache = {}          # (id(param), kind) -> _Packed

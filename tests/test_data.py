@@ -300,3 +300,63 @@ def test_trainer_on_an_image_folder(tmp_path, emu, device_data):
     assert all(np.isfinite(losses)) and not torch.equal(tr.arena.data, w0)
     b = tr._next_batch()
     assert b.shape == (2, 3, 16, 16) and b.dtype == torch.float32 and -1 <= float(b.min()) and float(b.max()) <= 1
+
+
+# ---- colddiff.data is the pipeline's home; colddiff.trainer re-exports it -----------------------------------------------------------
+MOVED = ["Recipe", "AUG1", "AUG2", "CENTER112", "CENTER_SHORT", "CIFAR_PAD", "RANDOM_AUG", "JITTER_STRIDE", "JITTER_LDS_CAP", "center_offset",
+         "resized", "Dataset", "Dataset_Aug1", "Dataset_Aug2", "DatasetCifar10", "SyntheticImages", "cycle", "CacheUnfit", "jitter_lds_bytes",
+         "draw_random_aug", "DeviceImageCache", "DeviceLoader", "make_grid", "write_grid", "save_image"]
+
+
+def test_trainer_reexports_every_moved_name():
+    import colddiff.data
+    import colddiff.trainer
+    for n in MOVED:
+        assert getattr(colddiff.trainer, n) is getattr(colddiff.data, n), n
+    public = {n for n, v in vars(colddiff.data).items() if not n.startswith("_") and getattr(v, "__module__", "colddiff.data") == "colddiff.data"
+              and not isinstance(v, type(os))}
+    assert public == set(MOVED), public ^ set(MOVED)                  # the list above is the whole module
+
+
+def test_data_imports_without_trainer_or_evaluate():
+    import subprocess
+    import sys
+    import colddiff
+    root = os.path.dirname(os.path.dirname(os.path.abspath(colddiff.__file__)))
+    code = ("import sys; import colddiff.data; bad = [m for m in ('colddiff.trainer', 'colddiff.evaluate') if m in sys.modules]; "
+            "assert not bad, bad; print('ok')")
+    r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, PYTHONPATH=root), capture_output=True, text=True)
+    assert r.returncode == 0 and r.stdout.strip() == "ok", r.stderr
+
+
+def test_one_step_body_three_ways(emu, tmp_path):
+    """The accumulate-and-backward body has three eager users; three Trainers from the same seeds run three optimizer steps each:
+    fused, the plain loop (`_fuse_off`), and the plain loop through a replaced `_loss`.  The two plain loops draw and compute the same
+    things in the same order: per-step loss and parameter arena are equal bit for bit.  The fused pass sums the same gradient in another
+    order: loss to 1e-5, every parameter to 1e-6, the bounds of test_modules.py::test_fused_accumulation_matches_oracle_micro_steps."""
+    from deblurring_diffusion_pytorch import GaussianDiffusion, Trainer, Unet
+    out = {}
+    for way in ("fused", "plain", "loss"):
+        torch.manual_seed(0)
+        with contextlib.redirect_stdout(io.StringIO()):
+            net = Unet(dim=16, dim_mults=(1, 2), channels=3)
+            diff = GaussianDiffusion(net, image_size=16, device_of_kernel="cpu", channels=3, timesteps=5, loss_type="l1", kernel_std=1.0,
+                                     kernel_size=3, blur_routine="Constant", train_routine="Final", sampling_routine="x0_step_down")
+            tr = Trainer(diff, None, image_size=16, train_batch_size=2, gradient_accumulate_every=2, dataset="synthetic",
+                         results_folder=str(tmp_path / way))
+        if way == "plain":
+            tr._fuse_off = True
+        elif way == "loss":
+            tr._loss = lambda batch, tr=tr: tr.core(batch)
+        assert tr._can_fuse() == (way == "fused") and not tr._can_prefetch()
+        torch.manual_seed(5)
+        losses = []
+        for _ in range(3):
+            losses.append(tr.train_step().clone())
+            tr.step += 1
+        assert tr.opt.step_count == 3
+        out[way] = (torch.stack(losses), tr.arena.data.clone())
+    assert torch.equal(out["plain"][0], out["loss"][0]) and torch.equal(out["plain"][1], out["loss"][1])
+    print("fused vs plain: loss", (out["fused"][0] - out["plain"][0]).abs().max().item(), "arena", (out["fused"][1] - out["plain"][1]).abs().max().item())
+    assert (out["fused"][0] - out["plain"][0]).abs().max() <= 1e-5
+    assert (out["fused"][1] - out["plain"][1]).abs().max() <= 1e-6

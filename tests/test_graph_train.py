@@ -267,6 +267,73 @@ def test_another_trainer_stepping_between_replays(monkeypatch, tmp_path):
     graphed(tg, 8)
 
 
+# ---- GraphStep without a Trainer ---------------------------------------------------------------------------------------------------
+def _standalone(raise_in_capture):
+    """buf <- 2 buf + s on 1024 floats, s = the step's uploaded scalar (0.5 n at step n): upload -> capture -> replay at its smallest."""
+    from colddiff import flat
+    from colddiff.graphstep import GraphStep
+    buf = torch.ones(1024, device=DEV)
+    host = {"n": 0, "capture_passes": 0}
+
+    def upload(table):
+        host["n"] += 1
+        table.upload(torch.tensor([0.5 * host["n"]] + [0.0] * 7), None, None)
+
+    def step(table):
+        if torch.cuda.is_current_stream_capturing():
+            host["capture_passes"] += 1
+            if raise_in_capture:
+                host["n"] += 7                       # host state and a CPU draw the pass must not keep
+                torch.rand(3)
+                raise RuntimeError("boom in the capture pass")
+        buf.mul_(2).add_(table.hp[0])
+        table.end_step()
+        return buf.sum()
+
+    def snapshot():
+        n = host["n"]
+        return lambda: host.update(n=n)
+    gs = _quiet(GraphStep, W, reason=lambda: None, signature=lambda: 0, table=lambda: flat.StepTable(torch.device(DEV), 0), upload=upload, step=step,
+                snapshot=snapshot)
+    return gs, buf, host
+
+
+def _recurrence(n_steps):
+    want = torch.ones(1024)
+    for n in range(1, n_steps + 1):
+        want = want * 2 + 0.5 * n
+    return want
+
+
+@pytest.mark.gpu
+def test_graphstep_standalone_upload_capture_replay():
+    gs, buf, host = _standalone(False)
+    for n in range(1, W + 4):                        # W eager graph-form steps, then the capture and three replays
+        out = _quiet(gs.step)
+        assert torch.equal(out.cpu(), _recurrence(n).sum()), n
+    torch.cuda.synchronize()
+    assert torch.equal(buf.cpu(), _recurrence(W + 3)) and host == {"n": W + 3, "capture_passes": 1}
+    assert gs.state() == {"mode": "graph", "reason": f"the step is captured after {W} warm-up steps", "captures": 1, "replays": 3}
+
+
+@pytest.mark.gpu
+def test_graphstep_standalone_capture_that_raises():
+    gs, buf, host = _standalone(True)
+    for _ in range(W):
+        assert _quiet(gs.step) is not None
+    torch.manual_seed(9)
+    cpu, cuda = torch.get_rng_state(), torch.cuda.get_rng_state(DEV)
+    for _ in range(3):                               # the pass that raises, and two more steps: no second attempt
+        assert _quiet(gs.step) is None
+    assert host == {"n": W, "capture_passes": 1}
+    assert torch.equal(torch.get_rng_state(), cpu) and torch.equal(torch.cuda.get_rng_state(DEV), cuda)
+    st = gs.state()
+    assert st["mode"] == "eager" and "boom in the capture pass" in st["reason"] and st["captures"] == 1 and st["replays"] == 0, st
+    assert gs.graph is None and gs.table is None
+    torch.cuda.synchronize()
+    assert torch.equal(buf.cpu(), _recurrence(W))    # the pass launched nothing
+
+
 # ---- the default path stays the default path --------------------------------------------------------------------------------------
 NEW = {"cdf_adam_step_dev", "cdf_groupnorm_fwd_ex_sd", "cdf_groupnorm_bwd_ex_sd", "cdf_dropout_sd", "cdf_adam_params"}
 
