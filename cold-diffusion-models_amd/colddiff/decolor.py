@@ -258,6 +258,9 @@ class DecolorDiffusion(TwoPhase, nn.Module):
         return self._chain(x_start, nsteps_b=t + 1)
 
     # -- sampling -------------------------------------------------------------------------------------
+    # sampler graph mode (colddiff/graphsample.py) is declined by this package and by the snowification package built on it
+    _SG_WHY = "the colour / snow reverse step takes host values per step (t.max(), the per-call forward-process state): not captured"
+
     @torch.no_grad()
     def sample_one_step(self, img, t, init_pred=None, _tmax=None):
         """One reverse step (diffusion.py:196-245).  `_tmax`: t.max() when the caller knows it (the samplers do: every row has the same
@@ -299,7 +302,8 @@ class DecolorDiffusion(TwoPhase, nn.Module):
             t_start = t_start - 1
 
     @torch.no_grad()
-    def sample(self, batch_size=16, img=None, t=None):
+    def sample(self, batch_size=16, img=None, t=None, graph=None):
+        self._sg_eager(graph, self._SG_WHY)
         self.forward_process.reset_parameters(batch_size=batch_size)
         if t == None:                                          # noqa: E711 (as upstream)
             t = self.num_timesteps
@@ -323,9 +327,10 @@ class DecolorDiffusion(TwoPhase, nn.Module):
         return {'xt': xt, 'direct_recons': direct_recons, 'recon': img}
 
     @torch.no_grad()
-    def all_sample(self, batch_size=16, img=None, t=None, times=None, res_dict=None, ends_only=False):
+    def all_sample(self, batch_size=16, img=None, t=None, times=None, res_dict=None, ends_only=False, graph=None):
         """diffusion.py:292-342.  `ends_only=True` (this engine's addition): -> (X_ts[0], X_0s[0], X_0s[-1]) of the full call, bit for
         bit, as device tensors -- the three the metric sweep reads -- without the other 2 T - 3 `lab2rgb` launches and host copies."""
+        self._sg_eager(graph, self._SG_WHY)
         self.forward_process.reset_parameters(batch_size=batch_size)
         if t == None:                                          # noqa: E711
             t = self.num_timesteps
@@ -430,7 +435,8 @@ class DecolorDiffusion(TwoPhase, nn.Module):
         return self.p_losses(x, t, None, *args, **kwargs)
 
     @torch.no_grad()
-    def forward_and_backward(self, batch_size=16, img=None, t=None, times=None, eval=True):
+    def forward_and_backward(self, batch_size=16, img=None, t=None, times=None, eval=True, graph=None):
+        self._sg_eager(graph, self._SG_WHY)
         self.denoise_fn.eval()
         if t == None:                                          # noqa: E711
             t = self.num_timesteps

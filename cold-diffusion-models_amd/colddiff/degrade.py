@@ -170,6 +170,35 @@ def blend_step(img, x1, x2, alphas, one_minus, t):
     return out
 
 
+# -- the device-step forms a replayed sampler graph launches (colddiff/graphsample.py): t = step[0] + 1 is read on the device ----------
+def noise_step_dev(img, x1, noise, ca, cb, step, est_noise):
+    img, x1 = _img(img), _img(x1)
+    noise = None if noise is None else _img(noise)
+    out = torch.empty_like(img)
+    rt.lib().cdf_noise_step_dev(P(img), P(x1), P(noise), P(ca), P(cb), P(step), ca.shape[0], 1 if est_noise else 0, P(out), img.numel(),
+                                rt.stream(img))
+    return out
+
+
+def blend_step_dev(img, x1, x2, alphas, one_minus, step):
+    img, x1, x2 = _img(img), _img(x1), _img(x2)
+    out = torch.empty_like(img)
+    rt.lib().cdf_blend_step_dev(P(img), P(x1), P(x2), P(alphas), P(one_minus), P(step), alphas.shape[0], P(out),
+                                img.shape[2] * img.shape[3], img.numel(), rt.stream(img))
+    return out
+
+
+def steps_advance(words, delta, floor):
+    """words = max(words + delta, floor) on the device (int64 words)."""
+    rt.lib().cdf_steps_advance(P(words), words.numel(), delta, floor, rt.stream(words))
+
+
+def traj_put(slab, src, slot):
+    """slab[slot[0]] = src, the slot read on the device; a slot outside the slab stores nothing."""
+    src = _img(src)
+    rt.lib().cdf_traj_put(P(slab), P(src), src.numel(), P(slot), slab.shape[0], rt.stream(slab))
+
+
 class _Loss(torch.autograd.Function):
     """mean |x_start - x_recon| (l1) or mean squared error (l2); gradient flows to x_recon only."""
 

@@ -16,6 +16,7 @@ from torch import nn
 
 from . import degrade as D
 from . import runtime as rt
+from .graphsample import SampleGraphMixin
 
 
 def _full_step(batch_size, value, device):
@@ -25,7 +26,7 @@ def _full_step(batch_size, value, device):
 # ===================================================================================================
 # deblurring
 # ===================================================================================================
-class TwoPhase:
+class TwoPhase(SampleGraphMixin):
     """forward() in two phases -- prepare() draws t exactly as forward() does and runs the degradation, loss_prepared() runs the
     network and the loss: prepare + loss_prepared == forward, same draws in the same order, same kernels.  The Trainer uses it to
     (a) degrade the next micro-batch on a side stream under the current forward / backward (deblurring) and (b) run the
@@ -189,8 +190,30 @@ class DeblurDiffusion(TwoPhase, nn.Module):
             return self._degrade(x, t, img=img)              # img - D(x,t) + D(x,t-1)
         return x
 
+    # -- sampler graph mode (graphsample.py): the reverse step with every `t` read from the step table -------------------
+    def _sg_why(self):
+        if not self._uniform():
+            return "blur_routine='Individual_Incremental' applies one kernel per step, picked by a host index"
+        if not D.blur_fits_lds(self.image_size, self.image_size, self.gaussian_kernels[0].weight.shape[-1]):
+            return "the plane is past the LDS cap: the per-step blur fallback takes host step counts"
+        if self.train_routine != 'Final':
+            return "train_routine is not 'Final'"
+        return None
+
+    def _sg_step(self, cur, tb):
+        x = self.denoise_fn(cur, tb.step)
+        if self.sampling_routine == 'default':
+            saved, self.discrete = self.discrete, False      # (as _reverse_step)
+            try:
+                return x, self._degrade(x, 0, t=tb.prev)      # D(x, t - 1): row -1 is the identity
+            finally:
+                self.discrete = saved
+        if self.sampling_routine == 'x0_step_down':
+            return x, self._degrade(x, 0, t=tb.step, img=cur)
+        return x, x
+
     @torch.no_grad()
-    def _sample_impl(self, batch_size, img, t, noise_level):
+    def _sample_impl(self, batch_size, img, t, noise_level, graph=None):
         self.denoise_fn.eval()
         if t is None:
             t = self.num_timesteps
@@ -199,11 +222,16 @@ class DeblurDiffusion(TwoPhase, nn.Module):
         if noise_level is not None:
             img = img + torch.randn_like(img) * noise_level
         xt = img
-        direct_recons, img = self._reverse_loop(batch_size, img, t)
+        direct_recons, img = self._reverse_loop(batch_size, img, t, graph)
         return xt, direct_recons, img
 
-    def _reverse_loop(self, batch_size, img, t):
+    def _reverse_loop(self, batch_size, img, t, graph=None):
         direct_recons = None
+        sg = self._sg(graph)
+        if sg is not None:
+            done = sg.reverse('reverse', self._sg_step, img, t, batch_size, why=self._sg_why())
+            if done is not None:
+                direct_recons, img, t, _ = done
         while t:
             step = _full_step(batch_size, t - 1, img.device)
             x = self.denoise_fn(img, step)
@@ -215,13 +243,13 @@ class DeblurDiffusion(TwoPhase, nn.Module):
             t = t - 1
         return direct_recons, img
 
-    def sample(self, batch_size=16, img=None, t=None):
-        out = self._sample_impl(batch_size, img, t, None)
+    def sample(self, batch_size=16, img=None, t=None, graph=None):
+        out = self._sample_impl(batch_size, img, t, None, graph)
         self.denoise_fn.train()
         return out
 
-    def gen_sample(self, batch_size=16, img=None, t=None, noise_level=0):
-        return self._sample_impl(batch_size, img, t, noise_level)
+    def gen_sample(self, batch_size=16, img=None, t=None, noise_level=0, graph=None):
+        return self._sample_impl(batch_size, img, t, noise_level, graph)
 
     gen_sample_2 = gen_sample
 
@@ -242,8 +270,9 @@ class DeblurDiffusion(TwoPhase, nn.Module):
         return out
 
     @torch.no_grad()
-    def forward_and_backward(self, batch_size=16, img=None, noise_level=0, t=None, times=None, eval=True):
+    def forward_and_backward(self, batch_size=16, img=None, noise_level=0, t=None, times=None, eval=True, graph=None):
         """The whole forward trajectory and every x_t on the way back (DEBLUR:692-770)."""
+        self._sg_eager(graph, "forward_and_backward keeps every step's image: not captured")
         if eval:
             self.denoise_fn.eval()
         if t is None:
@@ -279,9 +308,10 @@ class DeblurDiffusion(TwoPhase, nn.Module):
         return Forward, Backward, img
 
     @torch.no_grad()
-    def forward_and_backward_2(self, batch_size=16, img=None, noise_level=0, eval=True):
+    def forward_and_backward_2(self, batch_size=16, img=None, noise_level=0, eval=True, graph=None):
         """One forward trajectory, then back twice from the same x_T: with D(x0_hat, t-1) (written `img - img + ...`
         upstream) and with Algorithm 2 (DEBLUR:773-861)."""
+        self._sg_eager(graph, "forward_and_backward_2 keeps every step's image: not captured")
         if eval:
             self.denoise_fn.eval()
         T = self.num_timesteps
@@ -305,7 +335,7 @@ class DeblurDiffusion(TwoPhase, nn.Module):
         return Forward, runs[0][0], runs[1][0], runs[0][1], runs[1][1]
 
     @torch.no_grad()
-    def sample_from_blur(self, batch_size=16, img=None, t=None, times=None, eval=True, start=None):
+    def sample_from_blur(self, batch_size=16, img=None, t=None, times=None, eval=True, start=None, graph=None):
         """`sample` for an input that already carries kernels 0..start-1 (DEBLUR:864-925)."""
         if eval:
             self.denoise_fn.eval()
@@ -324,7 +354,7 @@ class DeblurDiffusion(TwoPhase, nn.Module):
                 img = self._apply_one(i, img)
         img = self._collapse(img)
         xt = img
-        direct_recons, img = self._reverse_loop(batch_size, img, t)
+        direct_recons, img = self._reverse_loop(batch_size, img, t, graph)
         return xt, direct_recons, img
 
     @torch.no_grad()
@@ -334,7 +364,7 @@ class DeblurDiffusion(TwoPhase, nn.Module):
         return self._forward_process(rt.check(img), t)
 
     @torch.no_grad()
-    def all_sample(self, batch_size=16, img=None, t=None, times=None, eval=True):
+    def all_sample(self, batch_size=16, img=None, t=None, times=None, eval=True, graph=None):
         if eval:
             self.denoise_fn.eval()
         if t is None:
@@ -348,6 +378,11 @@ class DeblurDiffusion(TwoPhase, nn.Module):
             img = self._collapse(img)
             noise = torch.randn_like(img) * 0.001
             img = img + noise
+        sg = self._sg(graph)
+        if sg is not None:
+            done = sg.reverse('all_sample', self._sg_step, img, times, batch_size, put='cur', why=self._sg_why())
+            if done is not None:
+                _, img, times, (X_0s, X_ts) = done
         while times:
             step = _full_step(batch_size, times - 1, img.device)
             x = self.denoise_fn(img, step)
@@ -456,9 +491,17 @@ class DenoiseDiffusion(TwoPhase, nn.Module):
         return (xt - ca.gather(-1, t).view(-1, 1, 1, 1) * x1_bar) / cb.gather(-1, t).view(-1, 1, 1, 1)
 
     @torch.no_grad()
-    def _reverse(self, batch_size, img, t, est_noise, noise):
+    def _reverse(self, batch_size, img, t, est_noise, noise, graph=None):
         ca, cb = self._tables()
         direct_recons = None
+        sg = self._sg(graph)
+        if sg is not None:
+            def step(cur, tb):
+                x1_bar = self.denoise_fn(cur, tb.step)
+                return x1_bar, D.noise_step_dev(cur, x1_bar, tb.st.get('noise'), ca, cb, tb.step, est_noise)
+            done = sg.reverse(('reverse', est_noise), step, img, t, batch_size, st={'noise': noise})
+            if done is not None:
+                direct_recons, img, t, _ = done
         while t:
             step = _full_step(batch_size, t - 1, img.device)
             x1_bar = self.denoise_fn(img, step)
@@ -468,29 +511,30 @@ class DenoiseDiffusion(TwoPhase, nn.Module):
             t = t - 1
         return direct_recons, img
 
-    def sample(self, batch_size=16, img=None, t=None):
+    def sample(self, batch_size=16, img=None, t=None, graph=None):
         # always the estimated-noise form, whatever sampling_routine says (DENOISE:342-375)
         self.denoise_fn.eval()
         t = self.num_timesteps if t is None else t
         xt = rt.check(img)
-        direct_recons, img = self._reverse(batch_size, xt, t, True, None)
+        direct_recons, img = self._reverse(batch_size, xt, t, True, None, graph)
         self.denoise_fn.train()
         return xt, direct_recons, img
 
-    def gen_sample(self, batch_size=16, img=None, t=None):
+    def gen_sample(self, batch_size=16, img=None, t=None, graph=None):
         self.denoise_fn.eval()
         t = self.num_timesteps if t is None else t
         noise = rt.check(img)
         direct_recons = None
         if self.sampling_routine == 'ddim':
-            direct_recons, img = self._reverse(batch_size, noise, t, True, None)
+            direct_recons, img = self._reverse(batch_size, noise, t, True, None, graph)
         elif self.sampling_routine == 'x0_step_down':
-            direct_recons, img = self._reverse(batch_size, noise, t, False, noise)
+            direct_recons, img = self._reverse(batch_size, noise, t, False, noise, graph)
         return noise, direct_recons, img
 
     @torch.no_grad()
-    def forward_and_backward(self, batch_size=16, img=None, t=None, times=None, eval=True):
+    def forward_and_backward(self, batch_size=16, img=None, t=None, times=None, eval=True, graph=None):
         """Noising trajectory with ONE noise draw, then the fixed-noise way back (DENOISE:438-479)."""
+        self._sg_eager(graph, "forward_and_backward keeps every step's image: not captured")
         self.denoise_fn.eval()
         t = self.num_timesteps if t is None else t
         ca, cb = self._tables()
@@ -510,7 +554,8 @@ class DenoiseDiffusion(TwoPhase, nn.Module):
         return Forward, Backward, img
 
     @torch.no_grad()
-    def all_sample(self, batch_size=16, img=None, t=None, times=None, eval=True):
+    def all_sample(self, batch_size=16, img=None, t=None, times=None, eval=True, graph=None):
+        self._sg_eager(graph, "all_sample moves every step to the host, as upstream does")
         if eval:
             self.denoise_fn.eval()
         t = self.num_timesteps if t is None else t
@@ -549,18 +594,19 @@ class DemixDiffusion(DenoiseDiffusion):
     """Same constructor, schedule, q_sample, p_losses, forward(x1, x2) and sample as the denoising class (the reference
     files differ only in the methods below, DEMIX vs DENOISE diff); `x2` is an image instead of Gaussian noise."""
 
-    def gen_sample(self, batch_size=16, img=None, noise_level=0, t=None):
+    def gen_sample(self, batch_size=16, img=None, noise_level=0, t=None, graph=None):
         # always the fixed-x2 form, whatever sampling_routine says (DEMIX:384-413)
         self.denoise_fn.eval()
         t = self.num_timesteps if t is None else t
         noise = rt.check(img)
         img = noise + torch.randn_like(noise) * noise_level
-        direct_recons, img = self._reverse(batch_size, img, t, False, noise)
+        direct_recons, img = self._reverse(batch_size, img, t, False, noise, graph)
         return noise, direct_recons, img
 
     @torch.no_grad()
-    def forward_and_backward(self, batch_size=16, img1=None, img2=None, t=None, times=None, eval=True):
+    def forward_and_backward(self, batch_size=16, img1=None, img2=None, t=None, times=None, eval=True, graph=None):
         """img1 mixed step by step into img2, then back with img2 held fixed (DEMIX:416-458)."""
+        self._sg_eager(graph, "forward_and_backward keeps every step's image: not captured")
         self.denoise_fn.eval()
         t = self.num_timesteps if t is None else t
         ca, cb = self._tables()
@@ -578,8 +624,8 @@ class DemixDiffusion(DenoiseDiffusion):
             t = t - 1
         return Forward, Backward, img
 
-    def all_sample(self, batch_size=16, img=None, t=None, times=None, eval=True):
-        X1_0s, _, X_ts = super().all_sample(batch_size=batch_size, img=img, t=t, times=times, eval=eval)
+    def all_sample(self, batch_size=16, img=None, t=None, times=None, eval=True, graph=None):
+        X1_0s, _, X_ts = super().all_sample(batch_size=batch_size, img=img, t=t, times=times, eval=eval, graph=graph)
         return X1_0s, X_ts                                            # (DEMIX:495)
 
 
@@ -638,8 +684,17 @@ class DefadeGenDiffusion(TwoPhase, nn.Module):
         return (xt - self.alphas[t] * x1_bar) / (self.one_minus_alphas[t] + 0.00000000000001)
 
     @torch.no_grad()
-    def _reverse(self, batch_size, img, t, x2, collect=None):
+    def _reverse(self, batch_size, img, t, x2, collect=None, graph=None):
         direct_recons = None
+        sg = self._sg(graph)
+        if sg is not None:
+            def step(cur, tb):
+                x1_bar = self.denoise_fn(cur, tb.step)
+                return x1_bar, D.blend_step_dev(cur, x1_bar, tb.st['x2'], self.alphas, self.one_minus_alphas, tb.step)
+            done = sg.reverse('reverse', step, img, t, batch_size, st={'x2': x2},
+                              why="every step's images are collected on the way: not captured" if collect is not None else None)
+            if done is not None:
+                direct_recons, img, t, _ = done
         while t:
             step = _full_step(batch_size, t - 1, img.device)
             x1_bar = self.denoise_fn(img, step)
@@ -651,24 +706,24 @@ class DefadeGenDiffusion(TwoPhase, nn.Module):
             t = t - 1
         return direct_recons, img
 
-    def sample(self, batch_size=16, img=None, t=None):               # DEFGEN:386-419 (x2 = the start image)
+    def sample(self, batch_size=16, img=None, t=None, graph=None):   # DEFGEN:386-419 (x2 = the start image)
         self.denoise_fn.eval()
         t = self.num_timesteps if t is None else t
         xt = rt.check(img)
-        direct_recons, img = self._reverse(batch_size, xt, t, xt)
+        direct_recons, img = self._reverse(batch_size, xt, t, xt, graph=graph)
         self.denoise_fn.train()
         return xt, direct_recons, img
 
-    def gen_sample(self, batch_size=16, img=None, noise_level=0, t=None):    # DEFGEN:428-457
+    def gen_sample(self, batch_size=16, img=None, noise_level=0, t=None, graph=None):    # DEFGEN:428-457
         self.denoise_fn.eval()
         t = self.num_timesteps if t is None else t
         noise = rt.check(img)
         img = noise + torch.randn_like(noise) * noise_level
-        direct_recons, img = self._reverse(batch_size, img, t, noise)
+        direct_recons, img = self._reverse(batch_size, img, t, noise, graph=graph)
         return noise, direct_recons, img
 
     @torch.no_grad()
-    def forward_and_backward(self, batch_size=16, img1=None, img2=None, t=None, times=None, eval=True):   # DEFGEN:460-504
+    def forward_and_backward(self, batch_size=16, img1=None, img2=None, t=None, times=None, eval=True, graph=None):   # DEFGEN:460-504
         self.denoise_fn.eval()
         t = self.num_timesteps if t is None else t
         img1, img2 = rt.check(img1), rt.check(img2)
@@ -676,17 +731,17 @@ class DefadeGenDiffusion(TwoPhase, nn.Module):
         for i in range(self.num_timesteps):                          # (the whole schedule, whatever t says: DEFGEN:475)
             Forward.append(self.q_sample(img1, img2, _full_step(batch_size, i, img1.device)))
         Backward = []
-        _, img = self._reverse(batch_size, img2, t, img2, collect=lambda x1, im: Backward.append(im))
+        _, img = self._reverse(batch_size, img2, t, img2, collect=lambda x1, im: Backward.append(im), graph=graph)
         return Forward, Backward, img
 
     @torch.no_grad()
-    def all_sample(self, batch_size=16, img=None, t=None, times=None, eval=True):       # DEFGEN:507-541
+    def all_sample(self, batch_size=16, img=None, t=None, times=None, eval=True, graph=None):       # DEFGEN:507-541
         if eval:
             self.denoise_fn.eval()
         t = self.num_timesteps if t is None else t
         img = rt.check(img)
         X1_0s, X_ts = [], []
-        self._reverse(batch_size, img, t, img, collect=lambda x1, im: (X1_0s.append(x1), X_ts.append(im)))
+        self._reverse(batch_size, img, t, img, collect=lambda x1, im: (X1_0s.append(x1), X_ts.append(im)), graph=graph)
         return X1_0s, X_ts
 
     def p_losses(self, x_start, x_end, t):
@@ -786,12 +841,33 @@ class ResolutionDiffusion(TwoPhase, nn.Module):
             x = self._step(x, i)
         return D.x0_step_down(img, x, prev) if img is not None else x
 
+    # -- sampler graph mode (graphsample.py) ------------------------------------------------------------------------------
+    def _sg_why(self):
+        if self._with_blur:
+            return "the *_with_blur routines run one launch per step from a host step count"
+        if self.train_routine != 'Final':
+            return "train_routine is not 'Final'"
+        return None
+
+    def _sg_step(self, cur, tb):
+        x = self.denoise_fn(cur, tb.step)
+        if self.sampling_routine == 'default':
+            return x, self._degrade(x, 0, t=tb.prev)
+        if self.sampling_routine == 'x0_step_down':
+            return x, self._degrade(x, 0, t=tb.step, img=cur)
+        return x, x
+
     @torch.no_grad()
-    def sample(self, batch_size=16, img=None, t=None):
+    def sample(self, batch_size=16, img=None, t=None, graph=None):
         if t is None:
             t = self.num_timesteps
         img = self._degrade(rt.check(img), t)
         xt, direct_recons = img, None
+        sg = self._sg(graph)
+        if sg is not None:
+            done = sg.reverse('reverse', self._sg_step, img, t, batch_size, why=self._sg_why())
+            if done is not None:
+                direct_recons, img, t, _ = done
         while t:
             step = _full_step(batch_size, t - 1, img.device)
             x = self.denoise_fn(img, step)
@@ -815,7 +891,7 @@ class ResolutionDiffusion(TwoPhase, nn.Module):
         return x
 
     @torch.no_grad()
-    def gen_sample(self, batch_size=16, img=None, t=None, times=None, noise_level=0):
+    def gen_sample(self, batch_size=16, img=None, t=None, times=None, noise_level=0, graph=None):
         """No forward process: `times` reverse updates from the given image (RESOL:460-505)."""
         if t is None:
             t = self.num_timesteps
@@ -825,6 +901,11 @@ class ResolutionDiffusion(TwoPhase, nn.Module):
         img = img + torch.randn_like(img) * noise_level
         direct_recons = None
         xt = img
+        sg = self._sg(graph)
+        if sg is not None:
+            done = sg.reverse('reverse', self._sg_step, img, times, batch_size, why=self._sg_why())
+            if done is not None:
+                direct_recons, img, times, _ = done
         while times:
             step = _full_step(batch_size, times - 1, img.device)
             x = self.denoise_fn(img, step)
@@ -835,7 +916,7 @@ class ResolutionDiffusion(TwoPhase, nn.Module):
         return xt, direct_recons, img
 
     @torch.no_grad()
-    def all_sample(self, batch_size=16, img=None, t=None, times=None):
+    def all_sample(self, batch_size=16, img=None, t=None, times=None, graph=None):
         """Every x0 estimate and every x_t of the reverse process (RESOL:508-556)."""
         if t is None:
             t = self.num_timesteps
@@ -843,6 +924,11 @@ class ResolutionDiffusion(TwoPhase, nn.Module):
             times = t
         img = self._degrade(rt.check(img), t)
         X_0s, X_ts = [], []
+        sg = self._sg(graph)
+        if sg is not None:
+            done = sg.reverse('all_sample', self._sg_step, img, times, batch_size, put='cur', why=self._sg_why())
+            if done is not None:
+                _, img, times, (X_0s, X_ts) = done
         while times:
             step = _full_step(batch_size, times - 1, img.device)
             x = self.denoise_fn(img, step)
@@ -853,8 +939,9 @@ class ResolutionDiffusion(TwoPhase, nn.Module):
         return X_0s, X_ts
 
     @torch.no_grad()
-    def forward_and_backward(self, batch_size=16, img=None, t=None, times=None, eval=True):
+    def forward_and_backward(self, batch_size=16, img=None, t=None, times=None, eval=True, graph=None):
         """The forward trajectory step by step, then every x_t on the way back (RESOL:559-617)."""
+        self._sg_eager(graph, "forward_and_backward keeps every step's image: not captured")
         if eval:
             self.denoise_fn.eval()
         if t is None:
@@ -996,7 +1083,7 @@ class DefadeDiffusion(TwoPhase, nn.Module):
         return rand_x, rand_y        # rows are cropped at rand_x, columns at rand_y (DEFADE:503-507)
 
     @torch.no_grad()
-    def _sample_impl(self, batch_size, faded, t, times, collect):
+    def _sample_impl(self, batch_size, faded, t, times, collect, graph=None):
         faded = rt.check(faded)
         masks = self._masks(faded.device)
         oy, ox = self._offsets(batch_size, faded.device)
@@ -1007,6 +1094,22 @@ class DefadeDiffusion(TwoPhase, nn.Module):
         faded = D.mask_chain(faded, masks, step_lo=0, step_hi=t - 1, off_y=oy, off_x=ox, quantise=self.discrete)
         xt, direct_recons, recon = faded, None, None
         x0_list, xt_list = [], []
+        sg = self._sg(graph)
+        if sg is not None:
+            def step(cur, tb):
+                x0 = self.defade_fn(cur, tb.step)
+                oy_, ox_ = tb.st.get('oy'), tb.st.get('ox')
+                if self.sampling_routine == 'default':
+                    return x0, D.mask_chain(x0, masks, t=tb.prev, off_y=oy_, off_x=ox_)
+                return x0, D.mask_chain(x0, masks, t=tb.step, img=cur, off_y=oy_, off_x=ox_)
+            why = None if self.sampling_routine in ('default', 'x0_step_down') else "unknown sampling_routine: the step is a no-op"
+            done = sg.reverse('all_sample' if collect else 'reverse', step, faded, times, batch_size, st={'oy': oy, 'ox': ox},
+                              put='next' if collect else None, why=why)
+            if done is not None:
+                direct_recons, faded, times, lists = done
+                recon = faded
+                if collect:
+                    x0_list, xt_list = lists
         while times:
             step = _full_step(batch_size, times - 1, faded.device)
             recon = self.defade_fn(faded, step)
@@ -1022,11 +1125,11 @@ class DefadeDiffusion(TwoPhase, nn.Module):
             times -= 1
         return (x0_list, xt_list) if collect else (xt, direct_recons, recon)
 
-    def sample(self, batch_size=16, faded_recon_sample=None, t=None):
-        return self._sample_impl(batch_size, faded_recon_sample, t, None, False)
+    def sample(self, batch_size=16, faded_recon_sample=None, t=None, graph=None):
+        return self._sample_impl(batch_size, faded_recon_sample, t, None, False, graph)
 
-    def all_sample(self, batch_size=16, faded_recon_sample=None, t=None, times=None):
-        return self._sample_impl(batch_size, faded_recon_sample, t, times, True)
+    def all_sample(self, batch_size=16, faded_recon_sample=None, t=None, times=None, graph=None):
+        return self._sample_impl(batch_size, faded_recon_sample, t, times, True, graph)
 
     def q_sample(self, x_start, t):
         x_start = rt.check(x_start)

@@ -1,6 +1,8 @@
 """`GraphStep` -- a step of device work replayed as ONE captured graph: upload -> [graph-form step: eagerly for the first `warmup` steps,
 captured once, replayed from then on].  Everything the step takes from the host lives in a flat.StepTable; the step advances NO host state, so
 the capture pass (which launches nothing) is not a step and the first replay is the next real step."""
+import gc
+
 import torch
 
 
@@ -54,8 +56,18 @@ class GraphStep:
         for gen in generators:
             g.register_generator_state(gen)
         table.rewind()
-        with torch.cuda.graph(g):
-            loss = self._step(table)
+        # A dead reference cycle that holds another captured graph (a core or Trainer nobody refers to any more) is destroyed when the
+        # cyclic collector gets to it.  Inside a capture pass that is a prohibited call and ends the process: collect before the pass,
+        # and keep the collector out of it (torch.cuda.graph does neither).
+        gc.collect()
+        was_enabled = gc.isenabled()
+        gc.disable()
+        try:
+            with torch.cuda.graph(g):
+                loss = self._step(table)
+        finally:
+            if was_enabled:
+                gc.enable()
         return g, loss
 
     def step(self):

@@ -72,7 +72,7 @@ class Trainer(EvalMixin):
     def __init__(self, diffusion_model, folder, *, ema_decay=0.995, image_size=128, train_batch_size=32, train_lr=2e-5,
                  train_num_steps=100000, gradient_accumulate_every=2, fp16=False, step_start_ema=2000, update_ema_every=10,
                  save_and_sample_every=1000, results_folder='./results', load_path=None, dataset=None, shuffle=True,
-                 num_workers=8, device_data=None, graph=None):
+                 num_workers=8, device_data=None, graph=None, sample_graph=None):
         super().__init__()
         assert not fp16, "apex fp16 is not supported (every reference script passes fp16=False)"
         # graph: replay the optimizer step as one captured graph where the Trainer is eligible (`_graph_reason`).  None = read
@@ -95,6 +95,10 @@ class Trainer(EvalMixin):
         self.image_size = self.core.image_size if self.image_size_from_model else image_size
         self.data_image_size = image_size
         self.ema_core = unwrap(self.ema_model)
+        # sample_graph: the samplers of the EMA core replay one captured reverse step (colddiff/graphsample.py).  None leaves the core's
+        # own switch (COLDDIFF_SAMPLE_GRAPH) as it is.
+        if sample_graph is not None and hasattr(self.ema_core, '_sg'):
+            self.ema_core.sample_graph = bool(sample_graph)
         # the denoising package feeds (image, fresh Gaussian noise) pairs (DENOISE:738-742)
         self.pair_noise = hasattr(self.core, 'sqrt_alphas_cumprod')
         self.device = next(self.core.parameters()).device

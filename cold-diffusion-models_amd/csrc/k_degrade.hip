@@ -556,8 +556,8 @@ __global__ void noise_qsample_kernel(const float* x0, const float* eps, const fl
 //   x2 = est_noise ? (img - ca[t-1]*x1) / cb[t-1] : noise
 //   xt_bar = ca[t-1]*x1 + cb[t-1]*x2 ; xt_sub1 = (t-1 != 0) ? ca[t-2]*x1 + cb[t-2]*x2 : x1
 //   out = img - xt_bar + xt_sub1
-__global__ void noise_step_kernel(const float* img, const float* x1, const float* noise, const float* ca,
-                                  const float* cb, int t, int est_noise, float* out, long long n) {
+__device__ __forceinline__ void noise_step_body(const float* img, const float* x1, const float* noise, const float* ca,
+                                                const float* cb, int t, int est_noise, float* out, long long n) {
     const float a1 = ca[t - 1], b1 = cb[t - 1];
     const float a2 = t - 1 != 0 ? ca[t - 2] : 0.f, b2 = t - 1 != 0 ? cb[t - 2] : 0.f;
     CDF_EW_LOOP(i, n) {
@@ -580,6 +580,21 @@ __global__ void noise_step_kernel(const float* img, const float* x1, const float
         out[i] = d + xt_sub1;
     }
 }
+__global__ void noise_step_kernel(const float* img, const float* x1, const float* noise, const float* ca,
+                                  const float* cb, int t, int est_noise, float* out, long long n) {
+    noise_step_body(img, x1, noise, ca, cb, t, est_noise, out, n);
+}
+// The step of a replayed sampler graph: t = step[0] + 1 read from DEVICE memory (the graph's step table, moved between replays by
+// cdf_steps_advance).  A word outside 0 .. T-1 indexes no table: out = img.
+__global__ void noise_step_dev_kernel(const float* img, const float* x1, const float* noise, const float* ca, const float* cb,
+                                      const int64_t* step, int T, int est_noise, float* out, long long n) {
+    const int64_t w = step[0];
+    if (w < 0 || w >= T) {
+        CDF_EW_LOOP(i, n) out[i] = img[i];
+        return;
+    }
+    noise_step_body(img, x1, noise, ca, cb, (int)w + 1, est_noise, out, n);
+}
 
 // Per-pixel blend of two images by mask tables [T][H*W] (the "defading generation" forward process,
 // defading-generation-diffusion-pytorch/defading_diffusion_pytorch/defading_diffusion_pytorch.py:543-548):
@@ -598,8 +613,8 @@ __global__ void blend_qsample_kernel(const float* x1, const float* x2, const flo
 
 // One reverse step with a FIXED second image x2 (same file :386-419, :428-457):
 //   xt_bar = al[t-1] x1 + om[t-1] x2 ; xt_sub1 = (t-1 != 0) ? al[t-2] x1 + om[t-2] x2 : x1 ; out = img - xt_bar + xt_sub1
-__global__ void blend_step_kernel(const float* img, const float* x1, const float* x2, const float* al, const float* om, int t, float* out,
-                                  long long HW, long long n) {
+__device__ __forceinline__ void blend_step_body(const float* img, const float* x1, const float* x2, const float* al, const float* om, int t,
+                                                float* out, long long HW, long long n) {
     const float* a1 = al + (long long)(t - 1) * HW;
     const float* o1 = om + (long long)(t - 1) * HW;
     const float* a2 = t - 1 != 0 ? al + (long long)(t - 2) * HW : a1;
@@ -617,6 +632,20 @@ __global__ void blend_step_kernel(const float* img, const float* x1, const float
         const float d = img[i] - xt_bar;
         out[i] = d + xt_sub1;
     }
+}
+__global__ void blend_step_kernel(const float* img, const float* x1, const float* x2, const float* al, const float* om, int t, float* out,
+                                  long long HW, long long n) {
+    blend_step_body(img, x1, x2, al, om, t, out, HW, n);
+}
+// ... with t = step[0] + 1 read from device memory; a word outside 0 .. T-1 indexes no table: out = img (see noise_step_dev_kernel)
+__global__ void blend_step_dev_kernel(const float* img, const float* x1, const float* x2, const float* al, const float* om,
+                                      const int64_t* step, int T, float* out, long long HW, long long n) {
+    const int64_t w = step[0];
+    if (w < 0 || w >= T) {
+        CDF_EW_LOOP(i, n) out[i] = img[i];
+        return;
+    }
+    blend_step_body(img, x1, x2, al, om, (int)w + 1, out, HW, n);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -818,6 +847,14 @@ extern "C" int cdf_noise_step(const float* img, const float* x1, const float* no
     return cdf_check_launch("noise_step");
 }
 
+extern "C" int cdf_noise_step_dev(const float* img, const float* x1, const float* noise, const float* ca, const float* cb,
+                                  const int64_t* step, int T, int est_noise, float* out, long long n, void* stream) {
+    CDF_REQUIRE(img && x1 && ca && cb && out && step && T >= 1 && n > 0, "cdf_noise_step_dev: bad args");
+    CDF_REQUIRE(est_noise || noise, "cdf_noise_step_dev: fixed-noise mode needs the noise tensor");
+    CDF_LAUNCH(noise_step_dev_kernel, dim3(cdf_ew_grid4k(n)), dim3(256), 0, CDF_S, img, x1, noise, ca, cb, step, T, est_noise, out, n);
+    return cdf_check_launch("noise_step_dev");
+}
+
 extern "C" int cdf_blend_qsample(const float* x1, const float* x2, const float* alphas, const float* one_minus, const int64_t* t,
                                  float* out, int B, int C, long long HW, void* stream) {
     CDF_REQUIRE(x1 && x2 && alphas && one_minus && t && out && B > 0 && C > 0 && HW > 0, "cdf_blend_qsample: bad args");
@@ -831,6 +868,13 @@ extern "C" int cdf_blend_step(const float* img, const float* x1, const float* x2
     CDF_REQUIRE(img && x1 && x2 && alphas && one_minus && out && t >= 1 && HW > 0 && n > 0, "cdf_blend_step: bad args");
     CDF_LAUNCH(blend_step_kernel, dim3(cdf_ew_grid4k(n)), dim3(256), 0, CDF_S, img, x1, x2, alphas, one_minus, t, out, HW, n);
     return cdf_check_launch("blend_step");
+}
+
+extern "C" int cdf_blend_step_dev(const float* img, const float* x1, const float* x2, const float* alphas, const float* one_minus,
+                                  const int64_t* step, int T, float* out, long long HW, long long n, void* stream) {
+    CDF_REQUIRE(img && x1 && x2 && alphas && one_minus && out && step && T >= 1 && HW > 0 && n > 0, "cdf_blend_step_dev: bad args");
+    CDF_LAUNCH(blend_step_dev_kernel, dim3(cdf_ew_grid4k(n)), dim3(256), 0, CDF_S, img, x1, x2, alphas, one_minus, step, T, out, HW, n);
+    return cdf_check_launch("blend_step_dev");
 }
 
 extern "C" int cdf_loss_fwd(const float* x, const float* y, float* out, float* partial /*>=1024 floats*/, long long n,

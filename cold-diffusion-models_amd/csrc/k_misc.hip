@@ -139,6 +139,22 @@ __global__ void ema_kernel(float* ma, const float* p, long long n, float beta, f
 __global__ void scale_kernel(float* x, long long n, float s) {
     CDF_EW_LOOP(i, n) x[i] = x[i] * s;
 }
+// The step counter of a replayed sampler graph: words[i] = max(words[i] + delta, floor).  The last node of the captured step; the
+// only thing that moves the counter between replays.
+__global__ void steps_advance_kernel(int64_t* words, int n, long long delta, long long floor) {
+    CDF_EW_LOOP(i, n) {
+        const long long w = (long long)words[i] + delta;
+        words[i] = (int64_t)(w < floor ? floor : w);
+    }
+}
+// slab[slot[0]][0 .. per_slot) = src: the trajectory store of a replayed sampler graph, indexed from device memory.  A slot outside
+// 0 .. n_slots-1 stores nothing.
+__global__ void traj_put_kernel(float* slab, const float* src, long long per_slot, const int64_t* slot, int n_slots) {
+    const int64_t s = slot[0];
+    if (s < 0 || s >= n_slots) return;
+    float* dst = slab + (long long)s * per_slot;
+    CDF_EW_LOOP(i, per_slot) dst[i] = src[i];
+}
 
 // ================================================================================================
 // ------------------------------------------------------------------------------------------------
@@ -346,6 +362,16 @@ extern "C" int cdf_scale(float* x, long long n, float s, void* stream) {
     CDF_REQUIRE(x && n > 0, "cdf_scale: bad args");
     CDF_LAUNCH(scale_kernel, dim3(cdf_ew_grid8k(n)), dim3(256), 0, CDF_S, x, n, s);
     return cdf_check_launch("scale");
+}
+extern "C" int cdf_steps_advance(int64_t* words, int n, long long delta, long long floor, void* stream) {
+    CDF_REQUIRE(words && n > 0, "cdf_steps_advance: bad args");
+    CDF_LAUNCH(steps_advance_kernel, dim3(cdf_ew_grid4k(n)), dim3(256), 0, CDF_S, words, n, delta, floor);
+    return cdf_check_launch("steps_advance");
+}
+extern "C" int cdf_traj_put(float* slab, const float* src, long long per_slot, const int64_t* slot, int n_slots, void* stream) {
+    CDF_REQUIRE(slab && src && slot && per_slot > 0 && n_slots > 0, "cdf_traj_put: bad args");
+    CDF_LAUNCH(traj_put_kernel, dim3(cdf_ew_grid4k(per_slot)), dim3(256), 0, CDF_S, slab, src, per_slot, slot, n_slots);
+    return cdf_check_launch("traj_put");
 }
 // bytes [0, bytes) of p zeroed with plain stores: 16-byte groups from the first aligned address, the ragged ends byte by byte
 __global__ void zero_kernel(unsigned char* p, long long bytes) {

@@ -28,7 +28,7 @@ extern "C" {
 /* Bumped whenever an exported signature changes incompatibly (rounds 1-3 all answered 1 while arguments were added: `tiled`,
  * `onepass`, `slots`, `tune`).  cdf_abi_version() returns the value the LIBRARY was built with; a binding compares it with the
  * header it was generated from before the first call (colddiff/_lib.py does) -- a mismatched pair would read shifted arguments. */
-#define CDF_ABI_VERSION 17
+#define CDF_ABI_VERSION 18
 
 #define CDF_E_INVALID (-1)
 #define CDF_E_UNSUPPORTED (-2)
@@ -87,6 +87,10 @@ int cdf_noise_qsample(const float* x0, const float* eps, const float* ca, const 
                       float* out, int B, long long per_sample, void* stream);
 int cdf_noise_step(const float* img, const float* x1, const float* noise, const float* ca, const float* cb, int t,
                    int est_noise, float* out, long long n, void* stream);
+/* cdf_noise_step with t = step[0] + 1 read from DEVICE memory (T = rows of ca / cb): the same arithmetic, bit-identical for the same
+ * t.  A word outside 0 .. T-1 indexes no table: out = img.  The step of a replayed sampler graph (colddiff/graphsample.py). */
+int cdf_noise_step_dev(const float* img, const float* x1, const float* noise, const float* ca, const float* cb, const int64_t* step,
+                       int T, int est_noise, float* out, long long n, void* stream);
 
 /* Per-pixel blend of two images by mask tables alphas / one_minus [T][H*W] ("defading generation":
  * defading-generation-diffusion-pytorch/defading_diffusion_pytorch/defading_diffusion_pytorch.py:543-548 q_sample;
@@ -95,6 +99,9 @@ int cdf_blend_qsample(const float* x1, const float* x2, const float* alphas, con
                       int B, int C, long long HW, void* stream);
 int cdf_blend_step(const float* img, const float* x1, const float* x2, const float* alphas, const float* one_minus, int t, float* out,
                    long long HW, long long n, void* stream);
+/* ... with t = step[0] + 1 read from device memory (T = rows of the mask tables); out = img for a word outside 0 .. T-1 */
+int cdf_blend_step_dev(const float* img, const float* x1, const float* x2, const float* alphas, const float* one_minus,
+                       const int64_t* step, int T, float* out, long long HW, long long n, void* stream);
 
 /* ---- colour forward process (decolor-diffusion/diffusion/forward_process_impl.py:131-218, diffusion.py:196-245, 344-388) --------------
  * DeColorization: up to T per-pixel 3 x 3 colour mixes (nn.Conv2d(3, 3, 1) upstream), optionally each wrapped in Lab <-> RGB conversions.
@@ -742,6 +749,10 @@ int cdf_adam_step_dev(float* p, const float* g, float* m, float* v, long long n,
 /* EMA.update_average (DEBLUR:78-81): ma = ma*beta + (1-beta)*p */
 int cdf_ema_update(float* ma, const float* p, long long n, double beta, void* stream);
 int cdf_scale(float* x, long long n, float s, void* stream);
+/* The device-side step counter of a replayed sampler graph: words[i] = max(words[i] + delta, floor), n words. */
+int cdf_steps_advance(int64_t* words, int n, long long delta, long long floor, void* stream);
+/* slab[slot[0]] = src (per_slot floats per slot, the slot read from device memory); a slot outside 0 .. n_slots-1 stores nothing. */
+int cdf_traj_put(float* slab, const float* src, long long per_slot, const int64_t* slot, int n_slots, void* stream);
 int cdf_zero(void* p, long long bytes, void* stream);
 
 #ifdef __cplusplus
