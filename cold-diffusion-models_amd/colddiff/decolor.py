@@ -260,6 +260,9 @@ class DecolorDiffusion(TwoPhase, nn.Module):
     # -- sampling -------------------------------------------------------------------------------------
     # sampler graph mode (colddiff/graphsample.py) is declined by this package and by the snowification package built on it
     _SG_WHY = "the colour / snow reverse step takes host values per step (t.max(), the per-call forward-process state): not captured"
+    # `sample` and `all_sample` keep loops of their own: their step is the public `sample_one_step`, which calls the network itself and
+    # takes the step vector, where the shared walk (SampleGraphMixin._walk, used by forward_and_backward) calls the network and asks the
+    # core for the update only
 
     @torch.no_grad()
     def sample_one_step(self, img, t, init_pred=None, _tmax=None):
@@ -446,15 +449,10 @@ class DecolorDiffusion(TwoPhase, nn.Module):
             n_img = self._chain(img, nsteps=i + 1)       # q_sample(img, full(i))
             Forward.append(n_img)
         Backward = []
-        img = n_img
-        while t:
-            step = _full_step(batch_size, t - 1, img.device)
-            x1_bar = self.denoise_fn(img, step)
-            Backward.append(img)
-            # img - q_sample(x1_bar, t - 1) + q_sample(x1_bar, t - 2): t steps, the state one step earlier, and the combine, in one launch
-            # (t - 1 == 0: xt_sub1_bar = x1_bar itself = the state after 0 steps)
-            img = self._chain(x1_bar, nsteps=t, nmax=t, img=img)
-            t = t - 1
+        # img - q_sample(x1_bar, t - 1) + q_sample(x1_bar, t - 2): t steps, the state one step earlier, and the combine, in one launch
+        # (t - 1 == 0: xt_sub1_bar = x1_bar itself = the state after 0 steps)
+        _, img = self._walk(n_img, t, batch_size, lambda x_t, x1_bar, t, tb: self._chain(x1_bar, nsteps=t, nmax=t, img=x_t),
+                            collect=lambda x1_bar, x_t: Backward.append(x_t))
         return Forward, Backward, img
 
 

@@ -1,14 +1,22 @@
-"""The four `GaussianDiffusion` classes of the cold-diffusion packages, on the HIP degradation kernels.
+"""The six `GaussianDiffusion` classes of the cold-diffusion packages, on the HIP degradation kernels.
 
 Constructor arguments, attribute names, method names, return values and `state_dict` layout follow
   deblurring  : deblurring_diffusion_pytorch.py:311-981
   denoising   : denoising_diffusion_pytorch.py:310-542
+  demixing    : demixing_diffusion_pytorch.py:309-502
+  defading generation : defading_diffusion_pytorch.py:309-568
   resolution  : resolution_diffusion_pytorch.py:325-767
   defading    : defading_diffusion_gaussian.py:298-554
 What differs is the execution: q_sample and every Alg.1/Alg.2 sampler step is ONE fused kernel
 launch (the whole step chain runs with the image plane resident in LDS) instead of O(T) convs, a
 torch.stack of T images and B python-level gathers, and nothing synchronises with the host
 (the reference's `torch.max(t)` -> `range()` does).
+
+What the six share is written once.  The reverse loop of every sampler is `SampleGraphMixin._walk` (graphsample.py): a sampler
+method does its forward process, hands the walk its core's step rule and, where it keeps per-step images, a collector, and packs
+the return value.  Each core has ONE `_update`, the `sampling_routine` / `train_routine` dispatch of a reverse step, with the
+ordinary form (host step count, `cdf_noise_step` / `cdf_blend_step`) and the captured form (the step table's rows, the `_dev`
+entry points) side by side.  `forward` and the 'Final' loss are `TwoPhase`'s (`TwoImage` for the cores with a second image).
 """
 import numpy as np
 import torch
@@ -61,6 +69,30 @@ class TwoPhase(SampleGraphMixin):
     def loss_prepared(self, prep):
         x_start, t, x_deg = prep
         return D.loss(x_start, self._network()(x_deg, t), self.loss_type)
+
+    def _final_loss(self, x_start, t, *x_end):
+        """The 'Final' training routine: the network's estimate from q_sample(x_start, [x_end,] t) against x_start."""
+        return self.loss_prepared((x_start, t, self.q_sample(x_start, *x_end, t)))
+
+    def p_losses(self, x_start, t):
+        if self.fusable():
+            return self._final_loss(x_start, t)
+        raise NotImplementedError()
+
+    def forward(self, x, *args, **kwargs):
+        return self.p_losses(x, self._draw_t(x), *args, **kwargs)
+
+
+class TwoImage(TwoPhase):
+    """TwoPhase for the cores whose forward process blends x1 into a second image: `forward(x1, x2)`, `p_losses(x_start, x_end, t)`."""
+
+    def p_losses(self, x_start, x_end, t):
+        if self.fusable():
+            return self._final_loss(x_start, t, x_end)
+        raise NotImplementedError()
+
+    def forward(self, x1, x2, *args, **kwargs):
+        return self.p_losses(x1, x2, self._draw_t(x1), *args, **kwargs)
 
 
 class DeblurDiffusion(TwoPhase, nn.Module):
@@ -145,14 +177,19 @@ class DeblurDiffusion(TwoPhase, nn.Module):
         k = m.weight.shape[-1]
         return D.blur_step(x, m.weight.detach()[:, 0].contiguous(), k, D.PAD_MODES[m.padding_mode])
 
-    def _degrade(self, x, nsteps, t=None, img=None, want_prev=False, quantise=False):
-        """D(x, nsteps): kernels 0..nsteps-1 (or 0..t[b] per sample), discrete mean-collapse included."""
+    def _fused(self, H, W):
+        """Is the blur chain ONE LDS-resident launch at this plane size (else: one launch per step, from host step counts)."""
+        return self._uniform() and D.blur_fits_lds(H, W, self.gaussian_kernels[0].weight.shape[-1])
+
+    def _degrade(self, x, nsteps, t=None, img=None, quantise=False, collapse=True):
+        """D(x, nsteps): kernels 0..nsteps-1 (or 0..t[b] per sample; with img: the Alg.2 combination), the discrete mean-collapse
+        included unless `collapse=False` drops it."""
         _, _, H, W = x.shape
-        collapse = self.num_timesteps - 1 if self.discrete else -1
-        if self._uniform() and D.blur_fits_lds(H, W, self.gaussian_kernels[0].weight.shape[-1]):
+        collapse = self.num_timesteps - 1 if self.discrete and collapse else -1
+        if self._fused(H, W):
             k = self.gaussian_kernels[0].weight.shape[-1]
             return D.blur_chain(x, self._taps(x.device), k, self._pad_mode(), t=t, step_lo=0, step_hi=nsteps - 1, img=img,
-                                want_prev=want_prev, collapse_step=collapse, quantise=quantise, taps1d=self._taps1d(x.device))
+                                collapse_step=collapse, quantise=quantise, taps1d=self._taps1d(x.device))
         assert t is None and not quantise, "per-sample t needs the LDS-resident path"
         prev = x
         for i in range(nsteps):
@@ -160,9 +197,7 @@ class DeblurDiffusion(TwoPhase, nn.Module):
             x = self._apply_one(i, x)
             if i == collapse:
                 x = D.plane_mean_(x)
-        if img is not None:
-            return D.x0_step_down(img, x, prev)
-        return (x, prev) if want_prev else x
+        return D.x0_step_down(img, x, prev) if img is not None else x
 
     def _collapse(self, img):
         return D.plane_mean_(img.clone()) if self.discrete else img
@@ -171,46 +206,44 @@ class DeblurDiffusion(TwoPhase, nn.Module):
     def _forward_process(self, img, t):
         if self.blur_routine == 'Individual_Incremental':
             return self._apply_one(t - 1, img)
-        saved, self.discrete = self.discrete, False          # the forward pass never mean-collapses inside the loop
-        try:
-            return self._degrade(img, t)
-        finally:
-            self.discrete = saved
+        return self._degrade(img, t, collapse=False)         # the forward pass never mean-collapses inside the loop
 
-    def _reverse_step(self, img, x, t):
-        if self.sampling_routine == 'default':
-            if self.blur_routine == 'Individual_Incremental':
-                return self._apply_one(t - 2, x)
-            saved, self.discrete = self.discrete, False      # Alg.1 chain has no collapse (DEBLUR:432-434)
-            try:
-                return self._degrade(x, t - 1)
-            finally:
-                self.discrete = saved
-        if self.sampling_routine == 'x0_step_down':
-            return self._degrade(x, t, img=img)              # img - D(x,t) + D(x,t-1)
+    def _update(self, img, x, t, tb=None, routine=None):
+        """The reverse step's rule, x_t = img and the estimate x -> x_{t-1}, under `routine` (default: the core's own; only
+        forward_and_backward_2 names one).  Ordinary form: `t` is the host step count; captured form: the step table `tb`."""
+        if routine is None:
+            if self.train_routine != 'Final':
+                return x
+            routine = self.sampling_routine
+            if routine == 'default' and not self._uniform():
+                return self._apply_one(t - 2, x)             # (one kernel per step, picked by a host index: never captured)
+        if routine == 'default':                             # D(x, t - 1); the Alg.1 chain has no collapse (DEBLUR:432-434)
+            if tb is not None:
+                return self._degrade(x, 0, t=tb.prev, collapse=False)      # row -1 is the identity
+            return self._degrade(x, t - 1, collapse=False)
+        if routine == 'x0_step_down':                        # img - D(x, t) + D(x, t - 1)
+            return self._degrade(x, 0, t=tb.step, img=img) if tb is not None else self._degrade(x, t, img=img)
         return x
 
-    # -- sampler graph mode (graphsample.py): the reverse step with every `t` read from the step table -------------------
+    def _update_xt_quirk(self, img, x, t, tb=None, any_routine=False):
+        """_update as all_sample and forward_and_backward apply it: under Individual_Incremental the reference blurs x_t instead of
+        the estimate -- all_sample whatever the sampling routine (DEBLUR:645-647), forward_and_backward under the two it knows
+        (DEBLUR:731-733, 744-746) -- and leaves the estimate alone at the last step."""
+        if self._uniform() or self.train_routine != 'Final':
+            return self._update(img, x, t, tb)
+        if t - 2 >= 0 and (any_routine or self.sampling_routine in ('default', 'x0_step_down')):
+            return self._apply_one(t - 2, img)
+        return x
+
     def _sg_why(self):
+        """Why the reverse step of this core cannot run with every `t` read from the step table (graphsample.py), or None."""
         if not self._uniform():
             return "blur_routine='Individual_Incremental' applies one kernel per step, picked by a host index"
-        if not D.blur_fits_lds(self.image_size, self.image_size, self.gaussian_kernels[0].weight.shape[-1]):
+        if not self._fused(self.image_size, self.image_size):
             return "the plane is past the LDS cap: the per-step blur fallback takes host step counts"
         if self.train_routine != 'Final':
             return "train_routine is not 'Final'"
         return None
-
-    def _sg_step(self, cur, tb):
-        x = self.denoise_fn(cur, tb.step)
-        if self.sampling_routine == 'default':
-            saved, self.discrete = self.discrete, False      # (as _reverse_step)
-            try:
-                return x, self._degrade(x, 0, t=tb.prev)      # D(x, t - 1): row -1 is the identity
-            finally:
-                self.discrete = saved
-        if self.sampling_routine == 'x0_step_down':
-            return x, self._degrade(x, 0, t=tb.step, img=cur)
-        return x, x
 
     @torch.no_grad()
     def _sample_impl(self, batch_size, img, t, noise_level, graph=None):
@@ -221,27 +254,11 @@ class DeblurDiffusion(TwoPhase, nn.Module):
         img = self._collapse(img)
         if noise_level is not None:
             img = img + torch.randn_like(img) * noise_level
-        xt = img
-        direct_recons, img = self._reverse_loop(batch_size, img, t, graph)
-        return xt, direct_recons, img
+        return (img,) + self._reverse_loop(batch_size, img, t, graph)
 
     def _reverse_loop(self, batch_size, img, t, graph=None):
-        direct_recons = None
-        sg = self._sg(graph)
-        if sg is not None:
-            done = sg.reverse('reverse', self._sg_step, img, t, batch_size, why=self._sg_why())
-            if done is not None:
-                direct_recons, img, t, _ = done
-        while t:
-            step = _full_step(batch_size, t - 1, img.device)
-            x = self.denoise_fn(img, step)
-            if self.train_routine == 'Final':
-                if direct_recons is None:
-                    direct_recons = x
-                x = self._reverse_step(img, x, t)
-            img = x
-            t = t - 1
-        return direct_recons, img
+        direct_recons, img = self._walk(img, t, batch_size, self._update, graph=graph, variant='reverse', why=self._sg_why)
+        return (direct_recons if self.train_routine == 'Final' else None), img
 
     def sample(self, batch_size=16, img=None, t=None, graph=None):
         out = self._sample_impl(batch_size, img, t, None, graph)
@@ -252,14 +269,6 @@ class DeblurDiffusion(TwoPhase, nn.Module):
         return self._sample_impl(batch_size, img, t, noise_level, graph)
 
     gen_sample_2 = gen_sample
-
-    def _chain(self, x, n, img=None, collapse=True):
-        """Kernels 0..n-1 on x (with img: the Alg.2 combination); `collapse=False` drops the discrete mean-collapse."""
-        saved, self.discrete = self.discrete, self.discrete and collapse
-        try:
-            return self._degrade(x, n, img=img)
-        finally:
-            self.discrete = saved
 
     def _trajectory(self, img, lo, hi):
         """[K_lo(img), K_{lo+1}(K_lo(img)), ...] for kernels lo..hi-1, one launch per step (any kernel size)."""
@@ -281,8 +290,7 @@ class DeblurDiffusion(TwoPhase, nn.Module):
             times = t
         img = rt.check(img)
         Forward = [img]
-        individual = self.blur_routine == 'Individual_Incremental'
-        if individual:
+        if self.blur_routine == 'Individual_Incremental':
             img = self._apply_one(t - 1, img)
         else:
             Forward += self._trajectory(img, 0, t)
@@ -291,20 +299,7 @@ class DeblurDiffusion(TwoPhase, nn.Module):
         if self.discrete:
             img = self._collapse(img)
             img = img + torch.randn_like(img) * noise_level
-        while times:
-            step = _full_step(batch_size, times - 1, img.device)
-            x = self.denoise_fn(img, step)
-            Backward.append(img)
-            if self.train_routine == 'Final':
-                if individual:
-                    if self.sampling_routine in ('default', 'x0_step_down') and times - 2 >= 0:
-                        x = self._apply_one(times - 2, img)           # reference quirk: blurs x_t (DEBLUR:731-733, 744-746)
-                elif self.sampling_routine == 'default':
-                    x = self._chain(x, times - 1, collapse=False)
-                elif self.sampling_routine == 'x0_step_down':
-                    x = self._chain(x, times, img=img)
-            img = x
-            times = times - 1
+        _, img = self._walk(img, times, batch_size, self._update_xt_quirk, collect=lambda x, x_t: Backward.append(x_t))
         return Forward, Backward, img
 
     @torch.no_grad()
@@ -321,18 +316,12 @@ class DeblurDiffusion(TwoPhase, nn.Module):
         if self.discrete:
             img = self._collapse(img)
             img = img + torch.randn_like(img) * noise_level
-        last_img = img
-        runs = []
-        for alg2 in (False, True):
-            img, times, back = last_img, T, []
-            while times:
-                step = _full_step(batch_size, times - 1, img.device)
-                x = self.denoise_fn(img, step)
-                back.append(img)
-                img = self._chain(x, times, img=img) if alg2 else self._chain(x, times - 1, collapse=False)
-                times = times - 1
-            runs.append((back, img))
-        return Forward, runs[0][0], runs[1][0], runs[0][1], runs[1][1]
+        backs, ends = [], []
+        for routine in ('default', 'x0_step_down'):
+            backs.append([])
+            ends.append(self._walk(img, T, batch_size, lambda x_t, x, t, tb, r=routine: self._update(x_t, x, t, tb, r),
+                                   collect=lambda x, x_t: backs[-1].append(x_t))[1])
+        return Forward, backs[0], backs[1], ends[0], ends[1]
 
     @torch.no_grad()
     def sample_from_blur(self, batch_size=16, img=None, t=None, times=None, eval=True, start=None, graph=None):
@@ -344,18 +333,14 @@ class DeblurDiffusion(TwoPhase, nn.Module):
         if start is None:
             start = 0
         img = rt.check(img)
-        H, W = img.shape[2:]
-        k = self.gaussian_kernels[0].weight.shape[-1]
-        if t > start and self._uniform() and D.blur_fits_lds(H, W, k):
-            img = D.blur_chain(img, self._taps(img.device), k, self._pad_mode(), step_lo=start, step_hi=t - 1,
-                               taps1d=self._taps1d(img.device))
+        if t > start and self._fused(*img.shape[2:]):
+            img = D.blur_chain(img, self._taps(img.device), self.gaussian_kernels[0].weight.shape[-1], self._pad_mode(), step_lo=start,
+                               step_hi=t - 1, taps1d=self._taps1d(img.device))
         else:
             for i in range(start, t):
                 img = self._apply_one(i, img)
         img = self._collapse(img)
-        xt = img
-        direct_recons, img = self._reverse_loop(batch_size, img, t, graph)
-        return xt, direct_recons, img
+        return (img,) + self._reverse_loop(batch_size, img, t, graph)
 
     @torch.no_grad()
     def opt(self, img, t=None):
@@ -378,34 +363,19 @@ class DeblurDiffusion(TwoPhase, nn.Module):
             img = self._collapse(img)
             noise = torch.randn_like(img) * 0.001
             img = img + noise
-        sg = self._sg(graph)
-        if sg is not None:
-            done = sg.reverse('all_sample', self._sg_step, img, times, batch_size, put='cur', why=self._sg_why())
-            if done is not None:
-                _, img, times, (X_0s, X_ts) = done
-        while times:
-            step = _full_step(batch_size, times - 1, img.device)
-            x = self.denoise_fn(img, step)
-            X_0s.append(x)
-            X_ts.append(img)
-            if self.train_routine == 'Final':
-                if self.blur_routine == 'Individual_Incremental':
-                    if times - 2 >= 0:
-                        x = self._apply_one(times - 2, img)       # reference quirk: blurs x_t (DEBLUR:645-647)
-                else:
-                    x = self._reverse_step(img, x, times)
-            img = x
-            times = times - 1
+        _, img = self._walk(img, times, batch_size, lambda x_t, x, t, tb: self._update_xt_quirk(x_t, x, t, tb, any_routine=True),
+                            collect=lambda x, x_t: (X_0s.append(x), X_ts.append(x_t)), graph=graph, variant='all_sample', put='cur',
+                            why=self._sg_why)
         if self.discrete:
             img = img - noise
         X_0s.append(img)
         self.denoise_fn.train()
         return X_0s, X_ts
 
-    # -- training (DEBLUR:927-981) --------------------------------------------------------------------------
+    # -- training (DEBLUR:927-981): p_losses and forward are TwoPhase's ------------------------------------------
     def q_sample(self, x_start, t):
         x_start = rt.check(x_start)
-        if self._uniform() and D.blur_fits_lds(x_start.shape[2], x_start.shape[3], self.gaussian_kernels[0].weight.shape[-1]):
+        if self._fused(*x_start.shape[2:]):
             return self._degrade(x_start, 0, t=t.contiguous(), quantise=self.discrete)
         # per-step fallback (varying kernel size / planes larger than LDS): blur to max(t), pick per sample
         max_iters = int(torch.max(t))
@@ -420,26 +390,13 @@ class DeblurDiffusion(TwoPhase, nn.Module):
             out = ((out + 1) * 0.5 * 255).int().float() / 255 * 2 - 1
         return out
 
-    def p_losses(self, x_start, t):
-        if self.train_routine == 'Final':
-            x_blur = self.q_sample(x_start=x_start, t=t)
-            x_recon = self.denoise_fn(x_blur, t)
-            return D.loss(x_start, x_recon, self.loss_type)
-        raise NotImplementedError()
-
-    def forward(self, x, *args, **kwargs):
-        b, c, h, w, device, img_size = *x.shape, x.device, self.image_size
-        assert h == img_size and w == img_size, f'height and width of image must be {img_size}'
-        t = torch.randint(0, self.num_timesteps, (b,), device=device).long()
-        return self.p_losses(x, t, *args, **kwargs)
-
     # -- forward() in two phases, for the Trainer's degradation prefetch: the blur chain of micro-batch i+1 (up to T sequential
     # steps on B*C planes: 96 of 256 CUs at B = 32) does not depend on the network and runs on a side stream under the
     # forward / backward of micro-batch i.  prepare() + loss_prepared() == forward(): same draws, same kernels.
     def can_prepare_async(self):
         """True when q_sample is ONE sync-free launch (uniform kernel size, plane fits the LDS): only then does a side-stream
         prefetch overlap with anything -- the per-step fallback reads max(t) on the host and would block the launching thread."""
-        return self._uniform() and D.blur_fits_lds(self.image_size, self.image_size, self.gaussian_kernels[0].weight.shape[-1])
+        return self._fused(self.image_size, self.image_size)
 
     def graph_safe(self):
         """Exactly when q_sample is the one fused launch: t is a device draw and the per-step fallback's int(torch.max(t)) is not reached."""
@@ -458,7 +415,7 @@ def cosine_beta_schedule(timesteps, s=0.008):
     return torch.clip(betas, 0, 0.999)
 
 
-class DenoiseDiffusion(TwoPhase, nn.Module):
+class DenoiseDiffusion(TwoImage, nn.Module):
     def __init__(self, denoise_fn, *, image_size, channels=3, timesteps=1000, loss_type='l1', train_routine='Final',
                  sampling_routine='default', discrete=False):
         super().__init__()
@@ -490,26 +447,18 @@ class DenoiseDiffusion(TwoPhase, nn.Module):
         ca, cb = self._tables()
         return (xt - ca.gather(-1, t).view(-1, 1, 1, 1) * x1_bar) / cb.gather(-1, t).view(-1, 1, 1, 1)
 
-    @torch.no_grad()
-    def _reverse(self, batch_size, img, t, est_noise, noise, graph=None):
+    def _update(self, img, x1_bar, t, tb, noise, est_noise):
+        """x_t = img and the estimate x1_bar -> x_{t-1}, with the second image estimated from x_t (`est_noise`) or held fixed (`noise`).
+        Ordinary form: `t` is the host step count; captured form: the step table `tb`, whose `st` holds the fixed image."""
         ca, cb = self._tables()
-        direct_recons = None
-        sg = self._sg(graph)
-        if sg is not None:
-            def step(cur, tb):
-                x1_bar = self.denoise_fn(cur, tb.step)
-                return x1_bar, D.noise_step_dev(cur, x1_bar, tb.st.get('noise'), ca, cb, tb.step, est_noise)
-            done = sg.reverse(('reverse', est_noise), step, img, t, batch_size, st={'noise': noise})
-            if done is not None:
-                direct_recons, img, t, _ = done
-        while t:
-            step = _full_step(batch_size, t - 1, img.device)
-            x1_bar = self.denoise_fn(img, step)
-            if direct_recons is None:
-                direct_recons = x1_bar
-            img = D.noise_step(img, x1_bar, noise, ca, cb, t, est_noise)
-            t = t - 1
-        return direct_recons, img
+        if tb is not None:
+            return D.noise_step_dev(img, x1_bar, tb.st.get('noise'), ca, cb, tb.step, est_noise)
+        return D.noise_step(img, x1_bar, noise, ca, cb, t, est_noise)
+
+    @torch.no_grad()
+    def _reverse(self, batch_size, img, t, est_noise, noise, graph=None, collect=None):
+        return self._walk(img, t, batch_size, lambda x_t, x, t, tb: self._update(x_t, x, t, tb, noise, est_noise), collect=collect,
+                          graph=graph, variant=('reverse', est_noise), st={'noise': noise})
 
     def sample(self, batch_size=16, img=None, t=None, graph=None):
         # always the estimated-noise form, whatever sampling_routine says (DENOISE:342-375)
@@ -532,26 +481,25 @@ class DenoiseDiffusion(TwoPhase, nn.Module):
         return noise, direct_recons, img
 
     @torch.no_grad()
-    def forward_and_backward(self, batch_size=16, img=None, t=None, times=None, eval=True, graph=None):
-        """Noising trajectory with ONE noise draw, then the fixed-noise way back (DENOISE:438-479)."""
+    def _forward_and_backward(self, batch_size, img, x2, t, graph):
+        """`img` mixed step by step into ONE second image (`x2`; None: a Gaussian draw), then back with that image held fixed."""
         self._sg_eager(graph, "forward_and_backward keeps every step's image: not captured")
         self.denoise_fn.eval()
         t = self.num_timesteps if t is None else t
         ca, cb = self._tables()
         img = rt.check(img)
+        noise = torch.randn_like(img) if x2 is None else rt.check(x2)
         Forward = [img]
-        noise = torch.randn_like(img)
         for i in range(t):
             n_img = D.noise_qsample(img, noise, ca, cb, _full_step(batch_size, i, img.device))
             Forward.append(n_img)
-        Backward, img = [], n_img
-        while t:
-            step = _full_step(batch_size, t - 1, img.device)
-            x1_bar = self.denoise_fn(img, step)
-            Backward.append(img)
-            img = D.noise_step(img, x1_bar, noise, ca, cb, t, False)
-            t = t - 1
+        Backward = []
+        _, img = self._reverse(batch_size, n_img, t, False, noise, graph=False, collect=lambda x1_bar, x_t: Backward.append(x_t))
         return Forward, Backward, img
+
+    def forward_and_backward(self, batch_size=16, img=None, t=None, times=None, eval=True, graph=None):
+        """Noising trajectory with ONE noise draw, then the fixed-noise way back (DENOISE:438-479)."""
+        return self._forward_and_backward(batch_size, img, None, t, graph)
 
     @torch.no_grad()
     def all_sample(self, batch_size=16, img=None, t=None, times=None, eval=True, graph=None):
@@ -559,31 +507,17 @@ class DenoiseDiffusion(TwoPhase, nn.Module):
         if eval:
             self.denoise_fn.eval()
         t = self.num_timesteps if t is None else t
-        ca, cb = self._tables()
         X1_0s, X2_0s, X_ts = [], [], []
-        while t:
-            step = _full_step(batch_size, t - 1, img.device)
-            x1_bar = self.denoise_fn(img, step)
-            x2_bar = self.get_x2_bar_from_xt(x1_bar, img, step)
+
+        def to_host(x1_bar, x_t):
+            step = _full_step(batch_size, t - 1 - len(X_ts), x_t.device)
+            x2_bar = self.get_x2_bar_from_xt(x1_bar, x_t, step)
             X1_0s.append(x1_bar.detach().cpu())
             X2_0s.append(x2_bar.detach().cpu())
-            X_ts.append(img.detach().cpu())
-            img = D.noise_step(img, x1_bar, None, ca, cb, t, True)
-            t = t - 1
+            X_ts.append(x_t.detach().cpu())
+
+        self._reverse(batch_size, img, t, True, None, graph=False, collect=to_host)
         return X1_0s, X2_0s, X_ts
-
-    def p_losses(self, x_start, x_end, t):
-        if self.train_routine == 'Final':
-            x_mix = self.q_sample(x_start=x_start, x_end=x_end, t=t)
-            x_recon = self.denoise_fn(x_mix, t)
-            return D.loss(x_start, x_recon, self.loss_type)
-        raise NotImplementedError()
-
-    def forward(self, x1, x2, *args, **kwargs):
-        b, c, h, w, device, img_size = *x1.shape, x1.device, self.image_size
-        assert h == img_size and w == img_size, f'height and width of image must be {img_size}'
-        t = torch.randint(0, self.num_timesteps, (b,), device=device).long()
-        return self.p_losses(x1, x2, t, *args, **kwargs)
 
 
 # ===================================================================================================
@@ -603,26 +537,9 @@ class DemixDiffusion(DenoiseDiffusion):
         direct_recons, img = self._reverse(batch_size, img, t, False, noise, graph)
         return noise, direct_recons, img
 
-    @torch.no_grad()
     def forward_and_backward(self, batch_size=16, img1=None, img2=None, t=None, times=None, eval=True, graph=None):
         """img1 mixed step by step into img2, then back with img2 held fixed (DEMIX:416-458)."""
-        self._sg_eager(graph, "forward_and_backward keeps every step's image: not captured")
-        self.denoise_fn.eval()
-        t = self.num_timesteps if t is None else t
-        ca, cb = self._tables()
-        img, noise = rt.check(img1), rt.check(img2)
-        Forward = [img]
-        for i in range(t):
-            n_img = D.noise_qsample(img, noise, ca, cb, _full_step(batch_size, i, img.device))
-            Forward.append(n_img)
-        Backward, img = [], n_img
-        while t:
-            step = _full_step(batch_size, t - 1, img.device)
-            x1_bar = self.denoise_fn(img, step)
-            Backward.append(img)
-            img = D.noise_step(img, x1_bar, noise, ca, cb, t, False)
-            t = t - 1
-        return Forward, Backward, img
+        return self._forward_and_backward(batch_size, img1, img2, t, graph)
 
     def all_sample(self, batch_size=16, img=None, t=None, times=None, eval=True, graph=None):
         X1_0s, _, X_ts = super().all_sample(batch_size=batch_size, img=img, t=t, times=times, eval=eval, graph=graph)
@@ -656,7 +573,7 @@ def get_reverse_kernels_with_schedule(timesteps, size, kernel_std, initial_mask)
     return torch.stack(out)
 
 
-class DefadeGenDiffusion(TwoPhase, nn.Module):
+class DefadeGenDiffusion(TwoImage, nn.Module):
     def __init__(self, denoise_fn, *, image_size, channels=3, timesteps=1000, loss_type='l1', train_routine='Final',
                  sampling_routine='default', reverse=False, kernel_std=0.15, initial_mask=11):
         super().__init__()
@@ -683,28 +600,18 @@ class DefadeGenDiffusion(TwoPhase, nn.Module):
     def get_x2_bar_from_xt(self, x1_bar, xt, t):
         return (xt - self.alphas[t] * x1_bar) / (self.one_minus_alphas[t] + 0.00000000000001)
 
+    def _update(self, img, x1_bar, t, tb, x2):
+        """x_t = img and the estimate x1_bar -> x_{t-1} with the second image x2 held fixed.  Ordinary form: `t` is the host step
+        count; captured form: the step table `tb`, whose `st` holds x2."""
+        if tb is not None:
+            return D.blend_step_dev(img, x1_bar, tb.st['x2'], self.alphas, self.one_minus_alphas, tb.step)
+        return D.blend_step(img, x1_bar, x2, self.alphas, self.one_minus_alphas, t)
+
     @torch.no_grad()
     def _reverse(self, batch_size, img, t, x2, collect=None, graph=None):
-        direct_recons = None
-        sg = self._sg(graph)
-        if sg is not None:
-            def step(cur, tb):
-                x1_bar = self.denoise_fn(cur, tb.step)
-                return x1_bar, D.blend_step_dev(cur, x1_bar, tb.st['x2'], self.alphas, self.one_minus_alphas, tb.step)
-            done = sg.reverse('reverse', step, img, t, batch_size, st={'x2': x2},
-                              why="every step's images are collected on the way: not captured" if collect is not None else None)
-            if done is not None:
-                direct_recons, img, t, _ = done
-        while t:
-            step = _full_step(batch_size, t - 1, img.device)
-            x1_bar = self.denoise_fn(img, step)
-            if direct_recons is None:
-                direct_recons = x1_bar
-            if collect is not None:
-                collect(x1_bar, img)
-            img = D.blend_step(img, x1_bar, x2, self.alphas, self.one_minus_alphas, t)
-            t = t - 1
-        return direct_recons, img
+        return self._walk(img, t, batch_size, lambda x_t, x, t, tb: self._update(x_t, x, t, tb, x2), collect=collect, graph=graph,
+                          variant='reverse', st={'x2': x2},
+                          why="every step's images are collected on the way: not captured" if collect is not None else None)
 
     def sample(self, batch_size=16, img=None, t=None, graph=None):   # DEFGEN:386-419 (x2 = the start image)
         self.denoise_fn.eval()
@@ -743,19 +650,6 @@ class DefadeGenDiffusion(TwoPhase, nn.Module):
         X1_0s, X_ts = [], []
         self._reverse(batch_size, img, t, img, collect=lambda x1, im: (X1_0s.append(x1), X_ts.append(im)), graph=graph)
         return X1_0s, X_ts
-
-    def p_losses(self, x_start, x_end, t):
-        if self.train_routine == 'Final':
-            x_mix = self.q_sample(x_start=x_start, x_end=x_end, t=t)
-            x_recon = self.denoise_fn(x_mix, t)
-            return D.loss(x_start, x_recon, self.loss_type)
-        raise NotImplementedError()
-
-    def forward(self, x1, x2, *args, **kwargs):
-        b, c, h, w, device, img_size = *x1.shape, x1.device, self.image_size
-        assert h == img_size and w == img_size, f'height and width of image must be {img_size}'
-        t = torch.randint(0, self.num_timesteps, (b,), device=device).long()
-        return self.p_losses(x1, x2, t, *args, **kwargs)
 
 
 # ===================================================================================================
@@ -849,71 +743,41 @@ class ResolutionDiffusion(TwoPhase, nn.Module):
             return "train_routine is not 'Final'"
         return None
 
-    def _sg_step(self, cur, tb):
-        x = self.denoise_fn(cur, tb.step)
+    def _update(self, img, x, t, tb=None):
+        """The reverse step's rule, x_t = img and the estimate x -> x_{t-1}.  Ordinary form: `t` is the host step count; captured
+        form: the step table `tb`."""
+        if self.train_routine != 'Final':
+            return x
         if self.sampling_routine == 'default':
-            return x, self._degrade(x, 0, t=tb.prev)
+            return self._degrade(x, 0, t=tb.prev) if tb is not None else self._degrade(x, t - 1)
         if self.sampling_routine == 'x0_step_down':
-            return x, self._degrade(x, 0, t=tb.step, img=cur)
-        return x, x
+            return self._degrade(x, 0, t=tb.step, img=img) if tb is not None else self._degrade(x, t, img=img)
+        return x
+
+    def _reverse(self, batch_size, img, n, graph, collect=None):
+        """`n` reverse steps from x_t = img (the samplers here do not call eval(), as upstream does not)."""
+        return self._walk(img, n, batch_size, self._update, collect=collect, graph=graph, variant='all_sample' if collect else 'reverse',
+                          put='cur' if collect else None, why=self._sg_why)
 
     @torch.no_grad()
     def sample(self, batch_size=16, img=None, t=None, graph=None):
         if t is None:
             t = self.num_timesteps
-        img = self._degrade(rt.check(img), t)
-        xt, direct_recons = img, None
-        sg = self._sg(graph)
-        if sg is not None:
-            done = sg.reverse('reverse', self._sg_step, img, t, batch_size, why=self._sg_why())
-            if done is not None:
-                direct_recons, img, t, _ = done
-        while t:
-            step = _full_step(batch_size, t - 1, img.device)
-            x = self.denoise_fn(img, step)
-            if self.train_routine == 'Final':
-                if direct_recons is None:
-                    direct_recons = x
-                if self.sampling_routine == 'default':
-                    x = self._degrade(x, t - 1)
-                elif self.sampling_routine == 'x0_step_down':
-                    x = self._degrade(x, t, img=img)
-            img = x
-            t = t - 1
-        return xt, direct_recons, img
-
-    def _reverse_update(self, img, x, times):
-        if self.train_routine == 'Final':
-            if self.sampling_routine == 'default':
-                return self._degrade(x, times - 1)
-            if self.sampling_routine == 'x0_step_down':
-                return self._degrade(x, times, img=img)
-        return x
+        xt = self._degrade(rt.check(img), t)
+        direct_recons, img = self._reverse(batch_size, xt, t, graph)
+        return xt, (direct_recons if self.train_routine == 'Final' else None), img
 
     @torch.no_grad()
     def gen_sample(self, batch_size=16, img=None, t=None, times=None, noise_level=0, graph=None):
-        """No forward process: `times` reverse updates from the given image (RESOL:460-505)."""
+        """No forward process: `times` reverse updates from the given image; `direct_recons` is set whatever train_routine is
+        (RESOL:460-505)."""
         if t is None:
             t = self.num_timesteps
         if times is None:
             times = t
         img = rt.check(img)
-        img = img + torch.randn_like(img) * noise_level
-        direct_recons = None
-        xt = img
-        sg = self._sg(graph)
-        if sg is not None:
-            done = sg.reverse('reverse', self._sg_step, img, times, batch_size, why=self._sg_why())
-            if done is not None:
-                direct_recons, img, times, _ = done
-        while times:
-            step = _full_step(batch_size, times - 1, img.device)
-            x = self.denoise_fn(img, step)
-            if direct_recons is None:
-                direct_recons = x
-            img = self._reverse_update(img, x, times)
-            times = times - 1
-        return xt, direct_recons, img
+        xt = img + torch.randn_like(img) * noise_level
+        return (xt,) + self._reverse(batch_size, xt, times, graph)
 
     @torch.no_grad()
     def all_sample(self, batch_size=16, img=None, t=None, times=None, graph=None):
@@ -924,18 +788,7 @@ class ResolutionDiffusion(TwoPhase, nn.Module):
             times = t
         img = self._degrade(rt.check(img), t)
         X_0s, X_ts = [], []
-        sg = self._sg(graph)
-        if sg is not None:
-            done = sg.reverse('all_sample', self._sg_step, img, times, batch_size, put='cur', why=self._sg_why())
-            if done is not None:
-                _, img, times, (X_0s, X_ts) = done
-        while times:
-            step = _full_step(batch_size, times - 1, img.device)
-            x = self.denoise_fn(img, step)
-            X_0s.append(x)
-            X_ts.append(img)
-            img = self._reverse_update(img, x, times)
-            times = times - 1
+        self._reverse(batch_size, img, times, graph, collect=lambda x, x_t: (X_0s.append(x), X_ts.append(x_t)))
         return X_0s, X_ts
 
     @torch.no_grad()
@@ -954,12 +807,7 @@ class ResolutionDiffusion(TwoPhase, nn.Module):
             img = self._step(img, i)
             Forward.append(img)
         Backward = []
-        while times:
-            step = _full_step(batch_size, times - 1, img.device)
-            x = self.denoise_fn(img, step)
-            Backward.append(img)
-            img = self._reverse_update(img, x, times)
-            times = times - 1
+        _, img = self._walk(img, times, batch_size, self._update, collect=lambda x, x_t: Backward.append(x_t))
         return Forward, Backward, img
 
     @torch.no_grad()
@@ -978,11 +826,6 @@ class ResolutionDiffusion(TwoPhase, nn.Module):
             x = self._step(x, i)
             out = torch.where((t == i).view(-1, 1, 1, 1), x, out)
         return out
-
-    def _final_loss(self, x_start, t):
-        x_blur = self.q_sample(x_start=x_start, t=t)
-        x_recon = self.denoise_fn(x_blur, t)
-        return D.loss(x_start, x_recon, self.loss_type)
 
     @staticmethod
     def _random_mean(x_start):
@@ -1023,12 +866,6 @@ class ResolutionDiffusion(TwoPhase, nn.Module):
             return D.loss(x_blur_sub, self.denoise_fn(x_blur, t), self.loss_type)
         raise UnboundLocalError("local variable 'loss' referenced before assignment")   # unknown routine upstream (RESOL:760)
 
-    def forward(self, x, *args, **kwargs):
-        b, c, h, w, device, img_size = *x.shape, x.device, self.image_size
-        assert h == img_size and w == img_size, f'height and width of image must be {img_size}'
-        t = torch.randint(0, self.num_timesteps, (b,), device=device).long()
-        return self.p_losses(x, t, *args, **kwargs)
-
 
 # ===================================================================================================
 # defading (Gaussian-mask inpainting)
@@ -1051,10 +888,7 @@ class DefadeDiffusion(TwoPhase, nn.Module):
         self.discrete = discrete
 
     def get_fade_kernel(self, dims, std):
-        fade_kernel = D.gaussian_kernel2d(dims, std)
-        fade_kernel = fade_kernel / torch.max(fade_kernel)
-        fade_kernel = torch.ones_like(fade_kernel) - fade_kernel
-        return fade_kernel[1:, 1:]
+        return get_fade_kernel(dims, std)
 
     def get_kernels(self):
         kernels, n = [], self.image_size
@@ -1082,8 +916,24 @@ class DefadeDiffusion(TwoPhase, nn.Module):
         rand_y = torch.randint(0, self.image_size + 1, (batch_size,), device=device).long()
         return rand_x, rand_y        # rows are cropped at rand_x, columns at rand_y (DEFADE:503-507)
 
+    def _update(self, img, x0, t, tb, masks, oy, ox):
+        """The reverse step's rule, x_t = img and the estimate x0 -> x_{t-1}.  Ordinary form: `t` is the host step count; captured
+        form: the step table `tb`, whose `st` holds the call's crop offsets."""
+        if tb is not None:
+            oy, ox = tb.st.get('oy'), tb.st.get('ox')
+        if self.sampling_routine == 'default':
+            if tb is not None:
+                return D.mask_chain(x0, masks, t=tb.prev, off_y=oy, off_x=ox)
+            return D.mask_chain(x0, masks, step_lo=0, step_hi=t - 2, off_y=oy, off_x=ox)
+        if self.sampling_routine == 'x0_step_down':
+            if tb is not None:
+                return D.mask_chain(x0, masks, t=tb.step, img=img, off_y=oy, off_x=ox)
+            return D.mask_chain(x0, masks, step_lo=0, step_hi=t - 1, img=img, off_y=oy, off_x=ox)
+        return img                                                   # an unknown routine leaves x_t where it is (never captured)
+
     @torch.no_grad()
     def _sample_impl(self, batch_size, faded, t, times, collect, graph=None):
+        """(the samplers here do not call eval(), as upstream does not; all_sample collects the NEXT x_t of every step)"""
         faded = rt.check(faded)
         masks = self._masks(faded.device)
         oy, ox = self._offsets(batch_size, faded.device)
@@ -1092,38 +942,13 @@ class DefadeDiffusion(TwoPhase, nn.Module):
         if times is None:
             times = t
         faded = D.mask_chain(faded, masks, step_lo=0, step_hi=t - 1, off_y=oy, off_x=ox, quantise=self.discrete)
-        xt, direct_recons, recon = faded, None, None
         x0_list, xt_list = [], []
-        sg = self._sg(graph)
-        if sg is not None:
-            def step(cur, tb):
-                x0 = self.defade_fn(cur, tb.step)
-                oy_, ox_ = tb.st.get('oy'), tb.st.get('ox')
-                if self.sampling_routine == 'default':
-                    return x0, D.mask_chain(x0, masks, t=tb.prev, off_y=oy_, off_x=ox_)
-                return x0, D.mask_chain(x0, masks, t=tb.step, img=cur, off_y=oy_, off_x=ox_)
-            why = None if self.sampling_routine in ('default', 'x0_step_down') else "unknown sampling_routine: the step is a no-op"
-            done = sg.reverse('all_sample' if collect else 'reverse', step, faded, times, batch_size, st={'oy': oy, 'ox': ox},
-                              put='next' if collect else None, why=why)
-            if done is not None:
-                direct_recons, faded, times, lists = done
-                recon = faded
-                if collect:
-                    x0_list, xt_list = lists
-        while times:
-            step = _full_step(batch_size, times - 1, faded.device)
-            recon = self.defade_fn(faded, step)
-            x0_list.append(recon)
-            if direct_recons is None:
-                direct_recons = recon
-            if self.sampling_routine == 'default':
-                faded = D.mask_chain(recon, masks, step_lo=0, step_hi=times - 2, off_y=oy, off_x=ox)
-            elif self.sampling_routine == 'x0_step_down':
-                faded = D.mask_chain(recon, masks, step_lo=0, step_hi=times - 1, img=faded, off_y=oy, off_x=ox)
-            recon = faded
-            xt_list.append(faded)
-            times -= 1
-        return (x0_list, xt_list) if collect else (xt, direct_recons, recon)
+        why = None if self.sampling_routine in ('default', 'x0_step_down') else "unknown sampling_routine: the step is a no-op"
+        direct_recons, recon = self._walk(faded, times, batch_size, lambda x_t, x0, t, tb: self._update(x_t, x0, t, tb, masks, oy, ox),
+                                          collect=(lambda x0, nxt: (x0_list.append(x0), xt_list.append(nxt))) if collect else None,
+                                          graph=graph, variant='all_sample' if collect else 'reverse', st={'oy': oy, 'ox': ox},
+                                          put='next' if collect else None, why=why)
+        return (x0_list, xt_list) if collect else (faded, direct_recons, recon if times else None)
 
     def sample(self, batch_size=16, faded_recon_sample=None, t=None, graph=None):
         return self._sample_impl(batch_size, faded_recon_sample, t, None, False, graph)
@@ -1136,14 +961,6 @@ class DefadeDiffusion(TwoPhase, nn.Module):
         oy, ox = self._offsets(x_start.size(0), x_start.device)
         return D.mask_chain(x_start, self._masks(x_start.device), t=t.contiguous(), off_y=oy, off_x=ox, quantise=self.discrete)
 
-    def p_losses(self, x_start, t):
-        x_fade = self.q_sample(x_start=x_start, t=t)
-        x_recon = self.defade_fn(x_fade, t)
-        return D.loss(x_start, x_recon, self.loss_type)
-
     def forward(self, x, *args, **kwargs):
-        b, c, h, w, device, img_size = *x.shape, x.device, self.image_size
-        assert h == img_size and w == img_size, f'height and width of image must be {img_size}'
-        t = torch.randint(0, self.num_timesteps, (b,), device=device).long()
-        self.fade_kernels = self.fade_kernels.to(device)
-        return self.p_losses(x, t, *args, **kwargs)
+        self._masks(x.device)                                        # (DEFADE's forward moves the masks to the batch's device)
+        return super().forward(x, *args, **kwargs)

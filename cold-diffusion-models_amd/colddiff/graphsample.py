@@ -16,7 +16,11 @@ machinery; what is specific to a sampler:
                 advances nothing), replays for the rest; a later call with the same signature replays every step.  A call of
                 t <= warm-up + 1 steps never captures: it runs the ordinary loop.
 The trajectory is bit-identical to the eager sampler's: the same kernels on the same values, `t` read from the table instead of
-passed by value.  noise_level draws, the forward process, eval() / train() stay outside, in the callers' order."""
+passed by value.  noise_level draws, the forward process, eval() / train() stay outside, in the callers' order.
+
+`SampleGraphMixin._walk` is the reverse loop of every sampler, captured or not: it tries `SampleGraph.reverse` where the caller
+describes the call for it, and runs what is left (all of it, by default) as the ordinary loop, with the core's `_update` as the
+step rule of both."""
 import os
 import weakref
 
@@ -206,6 +210,34 @@ class SampleGraphMixin:
         sg = self._sg(graph)
         if sg is not None:
             sg.why = why
+
+    def _walk(self, img, n, batch_size, update, collect=None, graph=None, variant=None, st=None, put=None, why=None):
+        """THE reverse walk of every sampler: `n` reverse steps from x_t = img -> (first x0 estimate, x_{t-n}).
+        `update(x_t, x0, t, tb) -> x_{t-1}` is the core's step rule in both of its forms: the ordinary loop hands it the host step
+        count `t` (tb None), a captured step the StepTable `tb` (t None).  `collect(x0, x_t)` sees every step; `put` = 'next' hands it
+        the step's result in place of its input.  `variant` names the call for SampleGraph.reverse (with `st`, `put`, `why`: its
+        arguments; `why` may be a callable, asked only in graph mode); a sampler that is never captured passes none and states its
+        reason through _sg_eager."""
+        net, direct_recons = self._network(), None
+        sg = self._sg(graph) if variant is not None else None
+        if sg is not None:
+            def step(cur, tb):
+                x = net(cur, tb.step)
+                return x, update(cur, x, None, tb)
+            done = sg.reverse(variant, step, img, n, batch_size, st=st, put=put, why=why() if callable(why) else why)
+            if done is not None:
+                direct_recons, img, n, lists = done
+                for x, x_t in zip(*(lists or ((), ()))):
+                    collect(x, x_t)
+        while n:
+            x = net(img, torch.full((batch_size,), n - 1, dtype=torch.long, device=img.device))
+            if direct_recons is None:
+                direct_recons = x
+            nxt = update(img, x, n, None)
+            if collect is not None:
+                collect(x, nxt if put == 'next' else img)
+            img, n = nxt, n - 1
+        return direct_recons, img
 
     def sample_graph_state(self):
         """{'mode': 'off' | 'eager' | 'graph', 'reason', 'captures', 'replays'}: 'eager' = graph mode was requested and the last

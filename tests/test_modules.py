@@ -260,6 +260,36 @@ def test_deblurring_sampler_variants_golden(mbe):
         _lists_close(X0, c["all_sample"][0], 1e-4), _lists_close(Xt, c["all_sample"][1], 1e-4)
 
 
+@pytest.mark.parametrize("sampling", ["default", "x0_step_down"])
+def test_deblurring_calls_leave_the_module_as_constructed(mbe, monkeypatch, sampling):
+    """No method passes an argument by assigning a module attribute: over every sampler, q_sample, forward and opt of a discrete core
+    the only attributes written are the kernel-stack cache, the sampler graph and nn.Module's `training`, and `discrete` -- which the
+    reverse step's chain must ignore and the forward process must honour -- is never touched."""
+    from deblurring_diffusion_pytorch import GaussianDiffusion, Unet
+    torch.manual_seed(5)
+    net = quiet(Unet, dim=8, dim_mults=(1, 2), channels=3).to(mbe.device)
+    d = GaussianDiffusion(net, image_size=8, device_of_kernel="cuda", channels=3, timesteps=3, kernel_std=0.5, kernel_size=3,
+                          sampling_routine=sampling, discrete=True).to(mbe.device)
+    x = mbe.to(torch.rand(2, 3, 8, 8) * 2 - 1)
+    written, plain = [], type(d).__setattr__
+
+    def spy(self, name, value):
+        written.append(name)
+        plain(self, name, value)
+
+    monkeypatch.setattr(type(d), "__setattr__", spy)
+    with torch.no_grad():
+        d.q_sample(x, mbe.to(torch.tensor([0, 2])))
+        d(x)
+        for method in ("sample", "gen_sample", "all_sample", "forward_and_backward", "forward_and_backward_2"):
+            getattr(d, method)(batch_size=2, img=x)
+        d.sample_from_blur(batch_size=2, img=x, start=1)
+        d.opt(x)
+    monkeypatch.undo()
+    assert set(written) <= {"_taps_cache", "_sample_graph", "training"}, sorted(set(written))
+    assert d.discrete is True
+
+
 def test_denoising_forward_and_backward(mbe):
     """DENOISE:438-479; its single randn_like draw is replayed from the same seed for the oracle."""
     from denoising_diffusion_pytorch import GaussianDiffusion
